@@ -5,7 +5,8 @@ Headline (`metric`, `value`): batch 2^20 Bandersnatch IETF-ECVRF verification fr
 (BASELINE.json configs[2]).  A "step" is one pass of the verify hot path (vrfhip_ietf_verify_batch_dev: checked
 decode -> Straus -> finish) over one batch of 2^20 synthetic proofs per GPU that already sit in HBM (SURVEY.md
 section 8d: seed_i = u64_le(i), sk_i = from_seed, msg_i = SHA512("vrfhip-msg" || u64_le(i))[..32], ad = "").
-The proofs themselves are produced by the GPU prove path before the timed region.
+The proofs themselves are produced by the GPU prove path before the timed region; about one in 16 of them is then
+forged (forgery_kinds), and the run fails unless every status is the one its forgery calls for.
 
 `python bench.py --gpus N` starts its own ranks when it is not already running under torch.distributed.run (the
 parent touches no GPU: it only spawns `python -m torch.distributed.run ... bench.py` and relays its output).
@@ -35,11 +36,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# HIP maps streams onto this many hardware queues (default 4); streams that share a queue run in order.  The
-# "in flight" configuration below wants its four streams on four queues (measured: two streams on one queue = no overlap).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 LOG2_BATCH = 20
+DUMP_MAX_ITEMS = 1 << 22          # --dump-outputs: larger outputs are written as a fixed, seeded sample of this many rows
+FORGE_EVERY = 16                  # about one headline proof in this many is forged (forgery_kinds)
+FORGED_STATUS = np.array([1, 1, 2], np.uint8)   # per forgery kind: VerificationFailure, VerificationFailure, InvalidData
 HBM_PEAK_GBS = 8000.0             # MI355X_MICROARCH.md: 8 TB/s
 VALU_INT_PEAK = 256 * 4 * 16 * 2.4e9   # lanes/s (microbench: profiles/r01_instr_rate_microbench.jsonl)
 # algorithmic bytes per unit
@@ -63,7 +64,26 @@ def parse_args():
                          "ONE global batch of 2^log2_batch items cut into N contiguous shards (BASELINE.json: '2^20 ... sharded "
                          "8x').  The other mode is measured in the same run and reported under `scaling_modes`.")
     ap.add_argument("--only", default="", help="comma-separated secondary legs to run (default: all)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline path returned in its last step (the verify "
+                         "statuses of the whole batch) as DIR/<name>.npy in float32, for output-by-output comparison of builds")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: {name: host array of rows}.  Writes DIR/<name>.npy as float32; an output of more than DUMP_MAX_ITEMS rows
+    is written as the rows of a fixed, seeded sample, with their indices in DIR/<name>_index.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.shape[0] > DUMP_MAX_ITEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_MAX_ITEMS, replace=False))
+            a = a[idx]
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
 
 
 def self_launch(args):
@@ -87,6 +107,19 @@ def synth_msgs(lo, n):
     for k in range(n):
         out[k] = np.frombuffer(hashlib.sha512(pre + int(lo + k).to_bytes(8, "little")).digest()[:32], np.uint8)
     return out
+
+
+def forgery_kinds(first, m):
+    """Which items [first, first + m) of the headline batch are forged, and how: -1 genuine; 0 a bit of c flipped, 1 a bit of
+    s flipped, 2 Gamma replaced by a non-canonical encoding (all bytes 0xff).  A verifier that accepted everything would
+    otherwise pass the bench, and its statuses would carry no information.  A fixed function of the global item index, so
+    every rank count and scaling mode forges the same items.  Each kind's status does not depend on the prevalidated flags."""
+    h = (np.arange(first, first + m, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(40)
+    return np.where(h % FORGE_EVERY == 0, (h // FORGE_EVERY) % 3, -1).astype(np.int8)
+
+
+def expected_status(kinds):
+    return np.where(kinds < 0, 0, FORGED_STATUS[np.maximum(kinds, 0)]).astype(np.uint8)
 
 
 def slim_results(res):
@@ -876,7 +909,7 @@ def cfg_pairing(D, args, ctx, want_cpu):
             "stage_ms_per_step": {"prep": ms[0], "msm_buckets": ms[1], "msm_final": ms[2], "pairing": ms[3]}}
     # steady state of a verifier that keeps four batches in flight: one context and one stream each, so that a
     # batch's latency-bound tail (bucket reduction + the single pairing: two waves, 12 ms) overlaps the others'
-    # MSMs.  Needs the streams on distinct hardware queues: GPU_MAX_HW_QUEUES (set at the top of this file).
+    # MSMs.  The overlap needs the streams on distinct hardware queues (the HIP runtime's queue count per process).
     m = 1 << 18
     extra = [type(ctx)(D.local) for _ in range(3)]
     lanes = []
@@ -974,16 +1007,36 @@ def run_rank(args):
     def verify_step(b):
         return lambda: ctx.ietf_verify_batch_dev(b["pk"], b["hh"], b["gamma"], b["c"], b["s"], b["status"])
 
+    def forged(b, first):
+        """The proofs of batch b with the items of forgery_kinds forged, and a status buffer of their own."""
+        k = torch.from_numpy(forgery_kinds(first, b["c"].shape[0])).to(dev)
+        c_, s_, g_ = b["c"].clone(), b["s"].clone(), b["gamma"].clone()
+        c_[k == 0, 8] ^= 1
+        s_[k == 1, 8] ^= 1
+        g_[k == 2] = 255
+        return dict(b, c=c_, s=s_, gamma=g_, status=torch.full_like(b["status"], 255))
+
+    def check_statuses(got, n_global):
+        """Every rank's statuses in global item order (weak: rank-major; strong: the shards in order) against the forgeries."""
+        want = expected_status(forgery_kinds(0, n_global))
+        got = got.cpu().numpy()
+        assert got.shape == want.shape and (got == want).all(), \
+            "%d of %d statuses differ from the forgeries' (%d forged)" % (int((got != want).sum()), n_global, int((want != 0).sum()))
+        return got
+
     # weak: every rank its own 2^log2_batch items.  strong: ONE global batch of 2^log2_batch items, rank g verifies the
     # contiguous shard sharding.shard_range gives it (BASELINE.json configs: "2^20 ... sharded 8x").  At N = 1 they coincide.
     from ark_ec_vrfs_amd.sharding import shard_range
     weak = make_batch(lo, n)
     s_lo, s_hi = shard_range(n, rank, world)
     strong = weak if world == 1 else make_batch(s_lo, s_hi - s_lo)
-    main_b, other_b = (strong, weak) if args.scaling == "strong" else (weak, strong)
+    # the timed legs verify copies in which forgery_kinds' items are forged; the secondary legs keep the genuine proofs
+    weak_h = forged(weak, lo)
+    strong_h = weak_h if world == 1 else forged(strong, s_lo)
+    main_b, other_b = (strong_h, weak_h) if args.scaling == "strong" else (weak_h, strong_h)
     main_n = (s_hi - s_lo) if args.scaling == "strong" else n
     main_global = n if args.scaling == "strong" else world * n
-    sk, msg, gamma, c, s, pk, hh, status = (weak[k] for k in ("sk", "msg", "gamma", "c", "s", "pk", "hh", "status"))
+    sk, msg, gamma, c, s, pk, hh = (weak[k] for k in ("sk", "msg", "gamma", "c", "s", "pk", "hh"))
     prove_s = weak["prove_s"]
 
     step = verify_step(main_b)
@@ -994,8 +1047,9 @@ def run_rank(args):
     elapsed, full = timed(D, step, args.steps, 0, gather_t=main_b["status"], n_per_rank=main_n, n_global=main_global)
     ctx.profile(False)
     stage_ms, groups = stage_avg(ctx)
-    n_bad = int((full != 0).sum())
-    assert n_bad == 0 and full.shape[0] == main_global, f"{n_bad} synthetic proofs failed to verify"
+    full = check_statuses(full, main_global)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"status": full})
     modes = {args.scaling: {"value": main_global * args.steps / elapsed, "ms_per_step": elapsed / args.steps * 1e3,
                             "global_batch": main_global, "items_per_gpu": main_global // world, "steps": args.steps}}
     other = "weak" if args.scaling == "strong" else "strong"
@@ -1006,17 +1060,18 @@ def run_rank(args):
         o_global = world * n if other == "weak" else n
         o_steps = max(3, args.config_steps)
         el_o, full_o = timed(D, verify_step(other_b), o_steps, 1, gather_t=other_b["status"], n_per_rank=o_n, n_global=o_global)
-        assert int((full_o != 0).sum()) == 0 and full_o.shape[0] == o_global
+        check_statuses(full_o, o_global)
         modes[other] = {"value": o_global * o_steps / el_o, "ms_per_step": el_o / o_steps * 1e3, "global_batch": o_global,
                         "items_per_gpu": o_global // world, "steps": o_steps}
-    step = verify_step(weak)                         # the secondary legs below run on the rank's own 2^log2_batch items
+    step = verify_step(weak_h)                       # the prevalidated leg: the rank's own 2^log2_batch items
 
     # the same batch with the points declared validated (typed Public/Input/Output values): round 1's operation
     preval = None
     if can_check and not args.prevalidated:
         ctx.set_prevalidated(True)
-        el_p, _ = timed(D, step, max(2, args.config_steps), 1, gather_t=status, n_per_rank=n)
+        el_p, full_p = timed(D, step, max(2, args.config_steps), 1, gather_t=weak_h["status"], n_per_rank=n)
         ctx.set_prevalidated(False)
+        check_statuses(full_p, world * n)
         preval = {"workload": "the headline batch with VRFHIP_FLAG_PREVALIDATED_* set: no subgroup test (typed, already "
                               "validated values -- the operation round 1 reported)",
                   "value": world * n * max(2, args.config_steps) / el_p, "unit": "verifies/s",
@@ -1065,10 +1120,11 @@ def run_rank(args):
             "scaling_modes": modes,
             "vs_baseline": None, "dtype": "u32", "data": "synthetic",
             "config": {"workload": "IETF ECVRF verify, Bandersnatch_SHA-512_ELL2, batch 2^%d %s, compressed points "
-                                   "(161 B/verify), %s, ad=\"\" (BASELINE.json configs[2])"
+                                   "(161 B/verify), %s, ad=\"\", about 1 in %d proofs forged (BASELINE.json configs[2])"
                                    % (args.log2_batch, "in total, cut into contiguous shards" if args.scaling == "strong" else "per GPU",
                                       "checked decode: on curve + prime-order subgroup, as arkworks' "
-                                      "deserialisation" if checked else "inputs declared pre-validated (no subgroup check)"),
+                                      "deserialisation" if checked else "inputs declared pre-validated (no subgroup check)",
+                                      FORGE_EVERY),
                        "global_batch": main_global, "parallelism": "items sharded x%d, result gather only" % world,
                        "subgroup_check": checked},
             "roofline": r, "valu": v, "pmc_stale": pmc_table()[1],
@@ -1079,7 +1135,7 @@ def run_rank(args):
         if preval:
             out["prevalidated"] = preval
         if want_cpu:
-            out["cpu_baseline"] = headline_cpu_baseline(args, pk, hh, gamma, c, s, status)
+            out["cpu_baseline"] = headline_cpu_baseline(args, pk, hh, weak_h["gamma"], weak_h["c"], weak_h["s"], weak_h["status"])
         if configs:
             out["configs"] = configs
         print_result(out, configs, world)

@@ -8,6 +8,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -185,3 +188,57 @@ def test_stale_profile_counters_are_not_attached(tmp_path):
     tab, why = b.pmc_table()
     committed = json.load(open(os.path.join(ROOT, "profiles", "pmc_kernels.json")))
     assert bool(tab) == ((committed.get("_stamp") or {}).get("source_sha256") == source_stamp()) and bool(tab) == (why is None)
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample_of_large_outputs(tmp_path):
+    """--dump-outputs: every output as DIR/<name>.npy in float32; one longer than DUMP_MAX_ITEMS rows goes out as the same
+    seeded sample of rows on every run, with the row indices beside it."""
+    b = _load_bench()
+    st = (np.arange(10) % 3).astype(np.uint8)
+    b.dump_outputs(str(tmp_path / "small"), {"status": st})
+    got = np.load(tmp_path / "small" / "status.npy")
+    assert got.dtype == np.float32 and (got == st).all() and not (tmp_path / "small" / "status_index.npy").exists()
+    b.DUMP_MAX_ITEMS = 4
+    big = np.arange(100, dtype=np.uint8)
+    for run in ("a", "b"):
+        b.dump_outputs(str(tmp_path / run), {"status": big})
+    idx = np.load(tmp_path / "a" / "status_index.npy")
+    rows = np.load(tmp_path / "a" / "status.npy")
+    assert idx.dtype == np.float64 and rows.dtype == np.float32 and rows.shape == (4,)
+    assert (np.diff(idx) > 0).all() and (rows == big[idx.astype(np.int64)]).all()
+    assert (idx == np.load(tmp_path / "b" / "status_index.npy")).all() and (rows == np.load(tmp_path / "b" / "status.npy")).all()
+
+
+def test_forgeries_are_fixed_by_the_item_index_and_cover_every_kind():
+    """The headline batch's forged items: about one in FORGE_EVERY, every kind present, and the same items whichever way the
+    global batch is cut into ranks or shards, so the gathered statuses of any run can be checked against one expectation."""
+    b = _load_bench()
+    n = 1 << 16
+    k = b.forgery_kinds(0, n)
+    assert set(np.unique(k)) == {-1, 0, 1, 2}
+    assert abs((k >= 0).mean() - 1 / b.FORGE_EVERY) < 0.01
+    assert (np.concatenate([b.forgery_kinds(lo, hi - lo) for lo, hi in ((0, 1000), (1000, 40000), (40000, n))]) == k).all()
+    want = b.expected_status(k)
+    assert (want[k < 0] == 0).all() and (want[k == 0] == 1).all() and (want[k == 1] == 1).all() and (want[k == 2] == 2).all()
+
+
+def test_steps_below_one_are_refused():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                         timeout=60)
+    assert out.returncode == 2 and "--steps" in out.stderr
+
+
+@pytest.mark.gpu
+def test_bench_times_the_asked_steps_and_dumps_the_last_one(tmp_path):
+    """One small run of the real timed path: the line reports the steps asked for and their ms_per_step, and the dump holds
+    the statuses of the whole batch: 0 for a genuine proof, the forgery's status for a forged one."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--log2-batch", "12", "--no-configs", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-4000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 3 and d["scaling_modes"]["weak"]["steps"] == 3 and d["ms_per_step"] > 0
+    st = np.load(tmp_path / "status.npy")
+    b = _load_bench()
+    want = b.expected_status(b.forgery_kinds(0, 1 << 12))
+    assert st.dtype == np.float32 and st.shape == (1 << 12,) and (st == want).all() and set(np.unique(st)) == {0, 1, 2}
