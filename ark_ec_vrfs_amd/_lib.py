@@ -28,6 +28,7 @@ SYMBOLS = [
     "vrfhip_ietf_prove_batch", "vrfhip_ietf_prove_batch_dev",
     "vrfhip_pedersen_prove_batch", "vrfhip_pedersen_prove_batch_dev",
     "vrfhip_pedersen_verify_batch", "vrfhip_pedersen_verify_batch_dev",
+    "vrfhip_pedersen_verify_batch_affine", "vrfhip_pedersen_verify_batch_affine_dev",
     "vrfhip_pedersen_verify_batch_rlc", "vrfhip_pedersen_verify_batch_rlc_dev",
     "vrfhip_pedersen_verify_batch_rlc_affine", "vrfhip_pedersen_verify_batch_rlc_affine_dev",
     "vrfhip_msm", "vrfhip_msm_dev",
@@ -42,6 +43,7 @@ SYMBOLS = [
     "vrfhip_debug_proofs_per_lane",
     "vrfhip_ietf_verify_batch_multi", "vrfhip_ietf_prove_batch_multi",
     "vrfhip_pedersen_prove_batch_multi", "vrfhip_pedersen_verify_batch_multi",
+    "vrfhip_ietf_verify_batch_affine_multi", "vrfhip_pedersen_verify_batch_affine_multi",
     "vrfhip_test_point_add", "vrfhip_test_scalar_mul", "vrfhip_test_sha512", "vrfhip_test_xmd", "vrfhip_test_batch_digest",
 ]
 
@@ -154,6 +156,8 @@ def load() -> ctypes.CDLL:
                                                      POINTER(c_int32)]
     lib.vrfhip_pedersen_verify_batch_rlc_dev.argtypes = [c_void_p, c_size_t, P, P, P, P, P, P, P, P, P, c_uint32,
                                                          P, P, P, c_void_p]
+    lib.vrfhip_pedersen_verify_batch_affine.argtypes = lib.vrfhip_pedersen_verify_batch.argtypes
+    lib.vrfhip_pedersen_verify_batch_affine_dev.argtypes = lib.vrfhip_pedersen_verify_batch_dev.argtypes
     lib.vrfhip_pedersen_verify_batch_rlc_affine.argtypes = lib.vrfhip_pedersen_verify_batch_rlc.argtypes
     lib.vrfhip_pedersen_verify_batch_rlc_affine_dev.argtypes = lib.vrfhip_pedersen_verify_batch_rlc_dev.argtypes
     lib.vrfhip_msm.argtypes = [c_void_p, c_size_t, P, P, P, P, P]
@@ -187,6 +191,8 @@ def load() -> ctypes.CDLL:
     lib.vrfhip_pedersen_prove_batch_multi.argtypes = [CP, c_int32, c_size_t, P, P, P, c_uint32, P, P, P, c_uint32,
                                                       P, P, P, P, P, P, P, P, P]
     lib.vrfhip_pedersen_verify_batch_multi.argtypes = [CP, c_int32, c_size_t, P, P, P, P, P, P, P, P, P, c_uint32, P, P]
+    lib.vrfhip_ietf_verify_batch_affine_multi.argtypes = lib.vrfhip_ietf_verify_batch_multi.argtypes
+    lib.vrfhip_pedersen_verify_batch_affine_multi.argtypes = lib.vrfhip_pedersen_verify_batch_multi.argtypes
     lib.vrfhip_test_point_add.argtypes = [c_void_p, c_size_t, P, P, P, P]
     lib.vrfhip_test_scalar_mul.argtypes = [c_void_p, c_size_t, P, P, P, P]
     lib.vrfhip_test_sha512.argtypes = [c_void_p, c_size_t, P, P, c_uint32, P]

@@ -485,6 +485,21 @@ class Context:
             "vrfhip_pedersen_verify_batch")
         return status
 
+    def pedersen_verify_batch_affine(self, inp_xy, out_xy, pk_com_xy, r_xy, ok_xy, s, sb, ad=b"") -> np.ndarray:
+        """`pedersen::Verifier::verify` from in-memory affine points: the five point arrays are (n, 64) x || y
+        (LE canonical, or arkworks Montgomery limbs under VRFHIP_FLAG_COORDS_MONT256); no square roots."""
+        arrs = [np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 64) for x in (inp_xy, out_xy, pk_com_xy, r_xy, ok_xy)]
+        arrs += [np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 32) for x in (s, sb)]
+        n = arrs[0].shape[0]
+        if not all(x.shape[0] == n for x in arrs):
+            raise ValueError("ragged batch")
+        status = np.empty(n, dtype=np.uint8)
+        blob, off, ad_len = self._ad_args(ad, n)
+        _lib.check(self._lib.vrfhip_pedersen_verify_batch_affine(
+            self._h, n, *[_ptr(x) for x in arrs], _ptr(blob), _ptr(off), ad_len, _ptr(status)),
+            "vrfhip_pedersen_verify_batch_affine")
+        return status
+
     def pedersen_verify_batch_rlc(self, inp, out, pk_com, r, ok, s, sb, ad=b"", seed: Optional[bytes] = None,
                                   affine: bool = False):
         """`pedersen::Verifier::verify` for a whole batch through one MSM (random linear combination).
@@ -540,6 +555,16 @@ class Context:
             self._h, inp.shape[0], inp.data_ptr(), out.data_ptr(), pk_com.data_ptr(), r.data_ptr(), ok.data_ptr(),
             s.data_ptr(), sb.data_ptr(), dp(ad), dp(ad_off), ad_len, status.data_ptr(), st),
             "vrfhip_pedersen_verify_batch_dev")
+
+    def pedersen_verify_batch_affine_dev(self, inp_xy, out_xy, pk_com_xy, r_xy, ok_xy, s, sb, status, ad=None, ad_off=None,
+                                         ad_len=0, stream=None):
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        dp = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self._lib.vrfhip_pedersen_verify_batch_affine_dev(
+            self._h, inp_xy.shape[0], inp_xy.data_ptr(), out_xy.data_ptr(), pk_com_xy.data_ptr(), r_xy.data_ptr(),
+            ok_xy.data_ptr(), s.data_ptr(), sb.data_ptr(), dp(ad), dp(ad_off), ad_len, status.data_ptr(), st),
+            "vrfhip_pedersen_verify_batch_affine_dev")
 
     def msm(self, bases_xy, scalars):
         """`VariableBaseMSM::msm`: sum_i scalars[i] * bases[i].  bases_xy: (n, 64) affine x||y LE;
@@ -817,6 +842,40 @@ def pedersen_verify_batch_multi(ctxs, inp, out, pk_com, r, ok, s, sb, ad=b"", rl
     _lib.check(_lib.load().vrfhip_pedersen_verify_batch_multi(arr, k, n, *[_ptr(x) for x in arrs], _ptr(blob), _ptr(off),
                                                               ad_len, _ptr(seed), _ptr(st)),
                "vrfhip_pedersen_verify_batch_multi")
+    return st
+
+
+def ietf_verify_batch_affine_multi(ctxs, pk_xy, inp_xy, out_xy, c, s, ad=b"") -> np.ndarray:
+    """vrfhip_ietf_verify_batch_affine_multi: ietf_verify_batch_multi over (n, 64) x || y points."""
+    pk, inp, out = (np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 64) for x in (pk_xy, inp_xy, out_xy))
+    c, s = (np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 32) for x in (c, s))
+    n = pk.shape[0]
+    if not all(x.shape[0] == n for x in (inp, out, c, s)):
+        raise ValueError("ragged batch")
+    blob, off, ad_len = Context._ad_args(ad, n)
+    st = np.empty(n, np.uint8)
+    arr, k = _ctx_array(ctxs)
+    _lib.check(_lib.load().vrfhip_ietf_verify_batch_affine_multi(arr, k, n, _ptr(pk), _ptr(inp), _ptr(out), _ptr(c), _ptr(s),
+                                                                 _ptr(blob), _ptr(off), ad_len, _ptr(st)),
+               "vrfhip_ietf_verify_batch_affine_multi")
+    return st
+
+
+def pedersen_verify_batch_affine_multi(ctxs, inp_xy, out_xy, pk_com_xy, r_xy, ok_xy, s, sb, ad=b"",
+                                       rlc_seed: Optional[bytes] = None) -> np.ndarray:
+    """vrfhip_pedersen_verify_batch_affine_multi: pedersen_verify_batch_multi over (n, 64) x || y points."""
+    arrs = [np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 64) for x in (inp_xy, out_xy, pk_com_xy, r_xy, ok_xy)]
+    arrs += [np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 32) for x in (s, sb)]
+    n = arrs[0].shape[0]
+    if not all(x.shape[0] == n for x in arrs):
+        raise ValueError("ragged batch")
+    blob, off, ad_len = Context._ad_args(ad, n)
+    st = np.empty(n, np.uint8)
+    seed = None if rlc_seed is None else _np_u8(rlc_seed, 32)
+    arr, k = _ctx_array(ctxs)
+    _lib.check(_lib.load().vrfhip_pedersen_verify_batch_affine_multi(arr, k, n, *[_ptr(x) for x in arrs], _ptr(blob),
+                                                                     _ptr(off), ad_len, _ptr(seed), _ptr(st)),
+               "vrfhip_pedersen_verify_batch_affine_multi")
     return st
 
 

@@ -1390,12 +1390,14 @@ int32_t vrfhip_pedersen_prove_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* sk
 }
 
 // ------------------------------------------------------------------------- Pedersen verify
-int32_t vrfhip_pedersen_verify_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_input,
-                                         const uint8_t* d_output, const uint8_t* d_pk_com,
-                                         const uint8_t* d_r, const uint8_t* d_ok, const uint8_t* d_s,
-                                         const uint8_t* d_sb, const uint8_t* d_ad,
-                                         const uint32_t* d_ad_off, uint32_t ad_len,
-                                         uint8_t* d_status, void* stream) {
+}  // extern "C"
+
+namespace {
+// affine: the five point arrays are 64-byte x || y (canonical, or Montgomery-256 under VRFHIP_FLAG_COORDS_MONT256)
+int32_t ped_verify_dev_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* d_input, const uint8_t* d_output,
+                            const uint8_t* d_pk_com, const uint8_t* d_r, const uint8_t* d_ok, const uint8_t* d_s,
+                            const uint8_t* d_sb, const uint8_t* d_ad, const uint32_t* d_ad_off, uint32_t ad_len,
+                            uint8_t* d_status, void* stream) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
   if (!d_input || !d_output || !d_pk_com || !d_r || !d_ok || !d_s || !d_sb || !d_status)
@@ -1407,13 +1409,16 @@ int32_t vrfhip_pedersen_verify_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_
   int32_t rc = ensure_workspace(ctx, n);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const int affine_in = affine ? (ctx->coords_mont256() ? 2 : 1) : 0;
   if (ctx->sw) {
+    const size_t pw = affine ? 64 : 33;
     for (size_t base = 0; base < n; base += ctx->ws_cap) {
       const size_t m = std::min(ctx->ws_cap, n - base);
       p256::PedVerifyArgs a;
       a.n = m;
-      a.h = d_input + base * 33; a.gamma = d_output + base * 33; a.pk_com = d_pk_com + base * 33;
-      a.r = d_r + base * 33; a.ok = d_ok + base * 33; a.s = d_s + base * 32; a.sb = d_sb + base * 32;
+      a.h = d_input + base * pw; a.gamma = d_output + base * pw; a.pk_com = d_pk_com + base * pw;
+      a.r = d_r + base * pw; a.ok = d_ok + base * pw; a.s = d_s + base * 32; a.sb = d_sb + base * 32;
+      a.affine_in = affine_in;
       a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
       a.status = d_status + base;
       a.ws = ctx->p256_ws;
@@ -1424,14 +1429,15 @@ int32_t vrfhip_pedersen_verify_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_
     HIP_TRY(hipGetLastError());
     return VRFHIP_SUCCESS;
   }
+  const size_t pw = affine ? 64 : ctx->pt_bytes();
   for (size_t base = 0; base < n; base += ctx->ws_cap) {
     size_t m = std::min(ctx->ws_cap, n - base);
     PedersenVerifyArgs a;
     a.suite = (int)ctx->suite;
     a.n = m;
-    const size_t pw = ctx->pt_bytes();
     a.h = d_input + base * pw; a.gamma = d_output + base * pw; a.pk_com = d_pk_com + base * pw;
     a.r = d_r + base * pw; a.ok = d_ok + base * pw; a.s = d_s + base * 32; a.sb = d_sb + base * 32;
+    a.affine_in = affine_in;
     a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
     a.check_mask = ctx->check_mask();
     a.status = d_status + base;
@@ -1444,11 +1450,9 @@ int32_t vrfhip_pedersen_verify_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_
   return VRFHIP_SUCCESS;
 }
 
-int32_t vrfhip_pedersen_verify_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* input,
-                                     const uint8_t* output, const uint8_t* pk_com, const uint8_t* r,
-                                     const uint8_t* ok, const uint8_t* s, const uint8_t* sb,
-                                     const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
-                                     uint8_t* status) {
+int32_t ped_verify_host_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* input, const uint8_t* output,
+                             const uint8_t* pk_com, const uint8_t* r, const uint8_t* ok, const uint8_t* s, const uint8_t* sb,
+                             const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len, uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
   if (!input || !output || !pk_com || !r || !ok || !s || !sb || !status)
@@ -1457,7 +1461,7 @@ int32_t vrfhip_pedersen_verify_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* i
   size_t adb = blob_bytes(n, ad_off, ad_len, true);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  const size_t pw = ctx->pt_bytes();
+  const size_t pw = affine ? 64 : ctx->pt_bytes();
   size_t need = 5 * Stage::pad(n * pw) + 2 * Stage::pad(n * 32) + Stage::pad(adb + 1) + Stage::pad((n + 1) * 4) + Stage::pad(n);
   int32_t rc = ensure_stage(ctx, need);
   if (rc) return rc;
@@ -1474,12 +1478,49 @@ int32_t vrfhip_pedersen_verify_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* i
   uint8_t* d_st = sg.take(n);
   if (adb) HIP_TRY(hipMemcpyAsync(d_ad, ad, adb, hipMemcpyHostToDevice, ctx->stream));
   if (ad_off) HIP_TRY(hipMemcpyAsync(d_off, ad_off, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  rc = vrfhip_pedersen_verify_batch_dev(ctx, n, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d_ad,
-                                        ad_off ? d_off : nullptr, ad_len, d_st, ctx->stream);
+  rc = ped_verify_dev_impl(ctx, n, affine, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d_ad, ad_off ? d_off : nullptr, ad_len,
+                           d_st, ctx->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return VRFHIP_SUCCESS;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t vrfhip_pedersen_verify_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_input,
+                                         const uint8_t* d_output, const uint8_t* d_pk_com,
+                                         const uint8_t* d_r, const uint8_t* d_ok, const uint8_t* d_s,
+                                         const uint8_t* d_sb, const uint8_t* d_ad,
+                                         const uint32_t* d_ad_off, uint32_t ad_len,
+                                         uint8_t* d_status, void* stream) {
+  return ped_verify_dev_impl(ctx, n, false, d_input, d_output, d_pk_com, d_r, d_ok, d_s, d_sb, d_ad, d_ad_off, ad_len,
+                             d_status, stream);
+}
+int32_t vrfhip_pedersen_verify_batch_affine_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_input_xy,
+                                                const uint8_t* d_output_xy, const uint8_t* d_pk_com_xy,
+                                                const uint8_t* d_r_xy, const uint8_t* d_ok_xy, const uint8_t* d_s,
+                                                const uint8_t* d_sb, const uint8_t* d_ad,
+                                                const uint32_t* d_ad_off, uint32_t ad_len,
+                                                uint8_t* d_status, void* stream) {
+  return ped_verify_dev_impl(ctx, n, true, d_input_xy, d_output_xy, d_pk_com_xy, d_r_xy, d_ok_xy, d_s, d_sb, d_ad, d_ad_off,
+                             ad_len, d_status, stream);
+}
+
+int32_t vrfhip_pedersen_verify_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* input,
+                                     const uint8_t* output, const uint8_t* pk_com, const uint8_t* r,
+                                     const uint8_t* ok, const uint8_t* s, const uint8_t* sb,
+                                     const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
+                                     uint8_t* status) {
+  return ped_verify_host_impl(ctx, n, false, input, output, pk_com, r, ok, s, sb, ad, ad_off, ad_len, status);
+}
+int32_t vrfhip_pedersen_verify_batch_affine(vrfhip_ctx* ctx, size_t n, const uint8_t* input_xy,
+                                            const uint8_t* output_xy, const uint8_t* pk_com_xy, const uint8_t* r_xy,
+                                            const uint8_t* ok_xy, const uint8_t* s, const uint8_t* sb,
+                                            const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
+                                            uint8_t* status) {
+  return ped_verify_host_impl(ctx, n, true, input_xy, output_xy, pk_com_xy, r_xy, ok_xy, s, sb, ad, ad_off, ad_len, status);
 }
 
 // ------------------------------------------------------------------------- Pedersen verify, batched (RLC)
@@ -2448,6 +2489,20 @@ size_t prove_point_bytes_of(vrfhip_ctx* const* ctxs, int32_t n_ctx) {
     if (!ctxs[g] || ctxs[g]->prove_point_bytes() != w) return 0;
   return w;
 }
+// the x || y entry points: all contexts must be of ONE suite (curve and suite id -- secp256r1 and bandersnatch_sw share the
+// 33-byte width, but their x || y are different coordinates) and agree on VRFHIP_FLAG_COORDS_MONT256
+bool affine_ctxs_agree(vrfhip_ctx* const* ctxs, int32_t n_ctx) {
+  if (!ctxs || n_ctx < 1 || !ctxs[0]) return true;            // run_sharded reports the bad argument
+  const vrfhip_suite_desc& d0 = ctxs[0]->desc;
+  for (int32_t g = 1; g < n_ctx; ++g) {
+    if (!ctxs[g]) return true;
+    const vrfhip_suite_desc& d = ctxs[g]->desc;
+    if (d.curve != d0.curve || d.suite_id_len != d0.suite_id_len || std::memcmp(d.suite_id, d0.suite_id, sizeof d.suite_id) != 0 ||
+        ctxs[g]->coords_mont256() != ctxs[0]->coords_mont256())
+      return false;
+  }
+  return true;
+}
 }  // namespace
 
 extern "C" {
@@ -2567,6 +2622,39 @@ int32_t vrfhip_pedersen_verify_batch_multi(vrfhip_ctx* const* ctxs, int32_t n_ct
                                               status + lo, nullptr);
     return vrfhip_pedersen_verify_batch(ctx, hi - lo, input + lo * pw, output + lo * pw, pk_com + lo * pw, r + lo * pw,
                                         ok + lo * pw, at32(s, lo), at32(sb, lo), a.blob, a.off, ad_len, status + lo);
+  });
+}
+
+int32_t vrfhip_ietf_verify_batch_affine_multi(vrfhip_ctx* const* ctxs, int32_t n_ctx, size_t n, const uint8_t* pk_xy,
+                                              const uint8_t* input_xy, const uint8_t* output_xy, const uint8_t* c,
+                                              const uint8_t* s, const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
+                                              uint8_t* status) {
+  if (n == 0) return VRFHIP_SUCCESS;
+  if (!pk_xy || !input_xy || !output_xy || !c || !s || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  if (!affine_ctxs_agree(ctxs, n_ctx)) return fail(VRFHIP_ERR_BAD_ARG, "contexts disagree on the suite or on VRFHIP_FLAG_COORDS_MONT256");
+  return run_sharded(ctxs, n_ctx, n, [&](vrfhip_ctx* ctx, size_t lo, size_t hi) {
+    BlobSlice a(ad, ad_off, ad_len, true, lo, hi);
+    return vrfhip_ietf_verify_batch_affine(ctx, hi - lo, pk_xy + lo * 64, input_xy + lo * 64, output_xy + lo * 64, at32(c, lo),
+                                           at32(s, lo), a.blob, a.off, ad_len, status + lo);
+  });
+}
+
+int32_t vrfhip_pedersen_verify_batch_affine_multi(vrfhip_ctx* const* ctxs, int32_t n_ctx, size_t n, const uint8_t* input_xy,
+                                                  const uint8_t* output_xy, const uint8_t* pk_com_xy, const uint8_t* r_xy,
+                                                  const uint8_t* ok_xy, const uint8_t* s, const uint8_t* sb, const uint8_t* ad,
+                                                  const uint32_t* ad_off, uint32_t ad_len, const uint8_t* rlc_seed,
+                                                  uint8_t* status) {
+  if (n == 0) return VRFHIP_SUCCESS;
+  if (!input_xy || !output_xy || !pk_com_xy || !r_xy || !ok_xy || !s || !sb || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  if (!affine_ctxs_agree(ctxs, n_ctx)) return fail(VRFHIP_ERR_BAD_ARG, "contexts disagree on the suite or on VRFHIP_FLAG_COORDS_MONT256");
+  return run_sharded(ctxs, n_ctx, n, [&](vrfhip_ctx* ctx, size_t lo, size_t hi) {
+    BlobSlice a(ad, ad_off, ad_len, true, lo, hi);
+    const size_t o = lo * 64;
+    if (rlc_seed)      // one multi-scalar multiplication per device slice; per-proof fallback inside the slice
+      return vrfhip_pedersen_verify_batch_rlc_affine(ctx, hi - lo, input_xy + o, output_xy + o, pk_com_xy + o, r_xy + o, ok_xy + o,
+                                                     at32(s, lo), at32(sb, lo), a.blob, a.off, ad_len, rlc_seed, status + lo, nullptr);
+    return vrfhip_pedersen_verify_batch_affine(ctx, hi - lo, input_xy + o, output_xy + o, pk_com_xy + o, r_xy + o, ok_xy + o,
+                                               at32(s, lo), at32(sb, lo), a.blob, a.off, ad_len, status + lo);
   });
 }
 

@@ -21,6 +21,7 @@ void launch_bsw_prove(const ProveArgs& a, hipStream_t st, hipEvent_t* ev = nullp
 // a.affine_in: pk, h, gamma as Weierstrass x || y; a.key_index: keyed verification (a.pk = the key set's encodings);
 // a.h_in_tabs must be 0; a.k_lane is not read
 void launch_bsw_ietf_verify(const VerifyArgs& a, hipStream_t st, hipEvent_t* ev = nullptr);
+// a.affine_in: the five points as Weierstrass x || y
 void launch_bsw_pedersen_verify(const PedersenVerifyArgs& a, hipStream_t st, hipEvent_t* ev = nullptr);
 void launch_bsw_keyset_build(size_t n_keys, uint8_t* pks, uint32_t* xy, uint8_t* valid, uint32_t* combs, uint32_t* prefix, DevTables T,
                              hipStream_t st);

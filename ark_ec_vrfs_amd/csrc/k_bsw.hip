@@ -379,9 +379,11 @@ __global__ void __launch_bounds__(BLOCK, 2) k_bsw_verify_finish(VerifyArgs a) {
 }
 
 // ---- Pedersen verify, stage 1: decode H, Gamma, pk_com, R, Ok; tables of the first three; affine R, Ok; challenge ----
-__global__ void __launch_bounds__(BLOCK, 2) k_bsw_ped_verify_decode(PedersenVerifyArgs a) {
-  size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= a.n) return;
+// AFFINE (a.affine_in: 1 canonical, 2 Montgomery-256): the five points come as Weierstrass x || y (64 bytes): range and
+// curve checks instead of the square roots, the same ONE map inversion; the encodings come out canonical.  A separate
+// instantiation, so that the compressed kernel keeps its registers.
+template <bool AFFINE>
+__device__ __forceinline__ void bsw_ped_verify_decode(const PedersenVerifyArgs& a, size_t i) {
   uint32_t* tabs = a.ws.tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS);
   uint32_t* pts = a.ws.pts + i * PROVE_PTS_WORDS;
   Enc33 enc[5];
@@ -396,9 +398,15 @@ __global__ void __launch_bounds__(BLOCK, 2) k_bsw_ped_verify_decode(PedersenVeri
 #pragma unroll 1
   for (int k = 0; k < 5; ++k) {
     const int p = k == 0 ? 2 : k == 1 ? 0 : k == 2 ? 1 : k;             // chain order: pk_com, H, Gamma, R, Ok
-    const Enc33 e = load33(p == 0 ? a.h : p == 1 ? a.gamma : p == 2 ? a.pk_com : p == 3 ? a.r : a.ok, i);
-    bits |= bsw_in_a(scr + k * BSW_SLOT, run, e, a.T.sq) << (2 * k);
-    const Enc33 ce = enc33_canonical(e);
+    const uint8_t* src = p == 0 ? a.h : p == 1 ? a.gamma : p == 2 ? a.pk_com : p == 3 ? a.r : a.ok;
+    Enc33 ce;
+    if constexpr (AFFINE) {
+      bits |= bsw_in_a_xy(scr + k * BSW_SLOT, run, ce, src, i, a.affine_in == 2) << (2 * k);
+    } else {
+      const Enc33 e = load33(src, i);
+      bits |= bsw_in_a(scr + k * BSW_SLOT, run, e, a.T.sq) << (2 * k);
+      ce = enc33_canonical(e);
+    }
 #pragma unroll
     for (int q = 0; q < 5; ++q)
       if (q == p) enc[q] = ce;
@@ -430,6 +438,16 @@ __global__ void __launch_bounds__(BLOCK, 2) k_bsw_ped_verify_decode(PedersenVeri
 #pragma unroll
   for (int j = 0; j < 8; ++j) aux[j] = c[j];
   a.ws.flags[i] = valid ? 1 : 0;
+}
+__global__ void __launch_bounds__(BLOCK, 2) k_bsw_ped_verify_decode(PedersenVerifyArgs a) {
+  size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  bsw_ped_verify_decode<false>(a, i);
+}
+__global__ void __launch_bounds__(BLOCK, 2) k_bsw_ped_verify_decode_affine(PedersenVerifyArgs a) {
+  size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  bsw_ped_verify_decode<true>(a, i);
 }
 
 // HALF 0: s*H - c*Gamma ; HALF 1: s*G - c*pk_com + sb*B
@@ -624,7 +642,8 @@ void launch_bsw_msm_out(const uint8_t* te_xy, uint8_t* out33, uint8_t* out_xy, u
 void launch_bsw_pedersen_verify(const PedersenVerifyArgs& a, hipStream_t st, hipEvent_t* ev) {
   if (a.n == 0) return;
   if (ev) (void)hipEventRecord(ev[0], st);
-  hipLaunchKernelGGL(k_bsw_ped_verify_decode, grid_for(a.n), dim3(BLOCK), 0, st, a);
+  if (a.affine_in) hipLaunchKernelGGL(k_bsw_ped_verify_decode_affine, grid_for(a.n), dim3(BLOCK), 0, st, a);
+  else hipLaunchKernelGGL(k_bsw_ped_verify_decode, grid_for(a.n), dim3(BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[1], st);
   hipLaunchKernelGGL(k_bsw_ped_verify_straus<0>, grid_for(a.n), dim3(BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[2], st);

@@ -405,6 +405,28 @@ __global__ void __launch_bounds__(P256_BLOCK) k_p256_ped_verify_decode(p256::Ped
   ws_store8(a.ws.sc, cap, i, 16, sb);
   a.ws.flags[i] = ok ? 1 : 0;
 }
+// the same stage for affine inputs (a.affine_in: the five points as 64-byte x || y): no square roots
+__global__ void __launch_bounds__(P256_BLOCK) k_p256_ped_verify_decode_affine(p256::PedVerifyArgs a) {
+  const size_t i = (size_t)blockIdx.x * P256_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const size_t cap = a.ws.cap;
+  const uint8_t* ad;
+  uint32_t ad_len;
+  bytes_lite_get(a.ad, i, ad, ad_len);
+  FeN x[5], y[5];
+  uint32_t c[8], s[8], sb[8];
+  const bool ok = p256_ped_verify_decode_affine_item(x, y, c, s, sb, a.h + i * 64, a.gamma + i * 64, a.pk_com + i * 64, a.r + i * 64,
+                                                     a.ok + i * 64, a.s + i * 32, a.sb + i * 32, ad, ad_len, a.affine_in == 2, a.str);
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    ws_store_fe(a.ws.aff, cap, i, j * 18, x[j]);
+    ws_store_fe(a.ws.aff, cap, i, j * 18 + 9, y[j]);
+  }
+  ws_store8(a.ws.sc, cap, i, 0, c);
+  ws_store8(a.ws.sc, cap, i, 8, s);
+  ws_store8(a.ws.sc, cap, i, 16, sb);
+  a.ws.flags[i] = ok ? 1 : 0;
+}
 // WHICH = 0: s H - c Gamma - Ok = O (two tables); 1: s G + sb B - c pk_com - R = O (two comb walks, one table).  The
 // verdict of each equation goes to word WHICH of the item's result record.
 template <int WHICH>
@@ -554,7 +576,8 @@ void launch_prove(const ProveArgs& a, hipStream_t st, hipEvent_t* ev) {
 void launch_pedersen_verify(const PedVerifyArgs& a, hipStream_t st, hipEvent_t* ev) {
   const unsigned g = blocks_for(a.n);
   if (ev) (void)hipEventRecord(ev[0], st);
-  hipLaunchKernelGGL(k_p256_ped_verify_decode, dim3(g), dim3(P256_BLOCK), 0, st, a);
+  if (a.affine_in) hipLaunchKernelGGL(k_p256_ped_verify_decode_affine, dim3(g), dim3(P256_BLOCK), 0, st, a);
+  else hipLaunchKernelGGL(k_p256_ped_verify_decode, dim3(g), dim3(P256_BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[1], st);
   hipLaunchKernelGGL(k_p256_ped_verify_mul<0>, dim3(g), dim3(P256_BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[2], st);

@@ -24,6 +24,25 @@ __global__ void __launch_bounds__(BLOCK, MINW) k_ped_verify_decode(PedersenVerif
   a.ws.flags[i] = ok ? 1 : 0;
 }
 
+// stage 1 for affine inputs (a.affine_in: the five points as 64-byte x || y): no square roots.  Fills the same
+// workspace slots as k_ped_verify_decode, so the Straus and finish stages run unchanged.
+template <class S, int MINW>
+__global__ void __launch_bounds__(BLOCK, MINW) k_ped_verify_decode_affine(PedersenVerifyArgs a) {
+  size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const uint8_t* ad; uint32_t ad_len;
+  bytes_get(a.ad, i, ad, ad_len);
+  uint32_t c[8];
+  bool ok = pedersen_verify_decode_affine_item<S>(c, a.T, a.h + i * 64, a.gamma + i * 64, a.pk_com + i * 64,
+                                                  a.r + i * 64, a.ok + i * 64, ad, ad_len,
+                                                  a.ws.tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS),
+                                                  a.ws.pts + i * PROVE_PTS_WORDS, a.check_mask, a.affine_in == 2);
+  uint32_t* aux = a.ws.aux + i * AUX_WORDS;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) aux[j] = c[j];
+  a.ws.flags[i] = ok ? 1 : 0;
+}
+
 // HALF 0: s*H - c*Gamma ; HALF 1: s*G - c*pk_com + sb*B.  Separate launches keep each wave uniform.
 template <class S, int HALF>
 __global__ void __launch_bounds__(BLOCK) k_ped_verify_straus(PedersenVerifyArgs a) {
@@ -73,7 +92,8 @@ __global__ void __launch_bounds__(BLOCK) k_ped_verify_finish(PedersenVerifyArgs 
 template <class S>
 static void launch_ped_t(const PedersenVerifyArgs& a, hipStream_t st, hipEvent_t* ev) {
   if (ev) (void)hipEventRecord(ev[0], st);
-  VRF_LAUNCH_MINW(k_ped_verify_decode, S, a.n, grid_for(a.n), 0, st, a);
+  if (a.affine_in) VRF_LAUNCH_MINW(k_ped_verify_decode_affine, S, a.n, grid_for(a.n), 0, st, a);
+  else VRF_LAUNCH_MINW(k_ped_verify_decode, S, a.n, grid_for(a.n), 0, st, a);
   if (ev) (void)hipEventRecord(ev[1], st);
   if (!ev && a.n <= STRAUS_FUSE_MAX_ITEMS) {
     dim3 g2 = grid_for(a.n);

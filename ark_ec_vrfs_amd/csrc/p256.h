@@ -78,7 +78,8 @@ struct ProveArgs {
 
 struct PedVerifyArgs {
   size_t n;
-  const uint8_t *h, *gamma, *pk_com, *r, *ok;   // n x 33 B Sec1
+  const uint8_t *h, *gamma, *pk_com, *r, *ok;   // n x 33 B Sec1 (affine_in != 0: n x 64 B x || y)
+  int affine_in;                                // 0: Sec1; 1: x || y little-endian canonical; 2: x || y arkworks Montgomery limbs
   const uint8_t *s, *sb;                        // n x 32 B big-endian
   BytesViewLite ad;
   uint8_t* status;

@@ -626,6 +626,37 @@ VRF_HD bool p256_ped_verify_decode_item(FeN (&x)[5], FeN (&y)[5], uint32_t c[8],
   const bool s_ok = p256_scalar_decode(s, s_be), sb_ok = p256_scalar_decode(sb, sb_be);
   return ok && s_ok && sb_ok;
 }
+// the same stage for callers that hold the five points as arkworks `Affine { x, y }` (64-byte x || y, little-endian canonical
+// integers, or arkworks' Montgomery limbs when mont256).  No square root: a coordinate >= p or a point off the curve is
+// InvalidData; the encodings the challenge hashes are rebuilt from (x, parity of y), as p256_verify_decode_affine_item does.
+VRF_HD bool p256_ped_verify_decode_affine_item(FeN (&x)[5], FeN (&y)[5], uint32_t c[8], uint32_t s[8], uint32_t sb[8],
+                                               const uint8_t* h_xy, const uint8_t* gamma_xy, const uint8_t* pk_com_xy,
+                                               const uint8_t* r_xy, const uint8_t* ok_xy, const uint8_t* s_be,
+                                               const uint8_t* sb_be, const uint8_t* ad, uint32_t ad_len, bool mont256,
+                                               const SuiteStr& ss) {
+  bool ok = true;
+  Sec1W enc[5];
+#pragma unroll 1
+  for (int j = 0; j < 5; ++j) {
+    const uint32_t* e = reinterpret_cast<const uint32_t*>(j == 0 ? h_xy : j == 1 ? gamma_xy : j == 2 ? pk_com_xy : j == 3 ? r_xy : ok_xy);
+    uint32_t xin[8], yin[8], xc[8], yc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { xin[i] = e[i]; yin[i] = e[8 + i]; }
+    const FeN xx = fe_from_abi(xc, xin, mont256), yy = fe_from_abi(yc, yin, mont256);
+    ok = !u256_ge_q(xin) && !u256_ge_q(yin) && sw_on_curve(xx, yy) && ok;
+    Sec1W w;
+    w.tag = 2u + (yc[0] & 1u);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w.xw[i] = xc[i];
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+      if (j == k) { x[k] = xx; y[k] = yy; enc[k] = w; }
+  }
+  const Sec1W pts[5] = {enc[2], enc[0], enc[1], enc[3], enc[4]};
+  p256_challenge(c, pts, ad, ad_len, ss);
+  const bool s_ok = p256_scalar_decode(s, s_be), sb_ok = p256_scalar_decode(sb, sb_be);
+  return ok && s_ok && sb_ok;
+}
 // verify, stage 2: the two equations as "is the point at infinity":  s H - c Gamma - Ok  and  s G + sb B - c pk_com - R
 VRF_HD bool sw_is_infinity(const PtW& p) { return fe_is_zero(p.Z); }
 VRF_HD bool p256_ped_verify_eq_h(const uint32_t* tabH, const uint32_t* tabG, size_t stride, const FeN& okx, const FeN& oky,

@@ -1668,6 +1668,56 @@ VRF_HD bool pedersen_verify_decode_item(uint32_t c_out[8], const DevTables& T,
   return valid;
 }
 
+// The same stage for callers that hold the five points in memory as arkworks `Affine { x, y }`: xy_h .. xy_ok are
+// 64-byte x || y (32-byte little-endian canonical integers; mont256: arkworks' in-memory Montgomery limbs).  No square
+// roots.  Validity = coordinates < q, the point on the curve and, under check_mask, in the prime-order subgroup.  The
+// challenge hashes the canonical encodings of the points.  Fills tabs and pts as pedersen_verify_decode_item does.
+template <class S>
+VRF_HD bool pedersen_verify_decode_affine_item(uint32_t c_out[8], const DevTables& T, const uint8_t* xy_h,
+                                               const uint8_t* xy_gamma, const uint8_t* xy_pk_com, const uint8_t* xy_r,
+                                               const uint8_t* xy_ok, const uint8_t* ad, uint32_t ad_len, uint32_t* tabs,
+                                               uint32_t* pts, uint32_t check_mask = 0, bool mont256 = false) {
+  uint32_t cp[5][8];
+  bool valid = true;
+#pragma unroll 1
+  for (int p = 0; p < 5; ++p) {
+    const uint8_t* src = p == 0 ? xy_h : p == 1 ? xy_gamma : p == 2 ? xy_pk_com : p == 3 ? xy_r : xy_ok;
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(src);
+    uint32_t xin[8], yin[8], xw[8], yw[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { xin[j] = w[j]; yin[j] = w[8 + j]; }
+    valid = valid && !u256_ge(xin, vrfk::Q32) && !u256_ge(yin, vrfk::Q32);
+    FeN x = fe_from_abi(xw, xin, mont256), y = fe_from_abi(yw, yin, mont256);     // xw, yw: canonical words
+    // a x^2 + y^2 = 1 + d x^2 y^2   <=>   a x^2 + y^2 - 1 = d (x y)^2
+    FeN x2 = fe_sqr(x), y2 = fe_sqr(y), xyv = fe_mul(x, y);
+    auto lhs = te_curve_lhs<S>(x2, y2);
+    valid = fe_eq(lhs, fe_mul(fe_mul(fe_sqr(xyv), S::d()), fe_one())) && valid;
+    // check_mask: H is an input, Gamma an output, pk_com / R / Ok proof points
+    if (check_mask & (p == 0 ? CHK_INPUT : p == 1 ? CHK_OUTPUT : CHK_PROOF)) valid = in_prime_subgroup<S>(x, y, T.sq) && valid;
+    if (p < 3) {
+      build_glv_tables<S>(tabs + p * 2 * WIN_TABLE_WORDS, x, y);
+    } else {
+      uint32_t* dst = pts + (p == 3 ? PED_R_OFF : PED_OK_OFF);
+      fe_store(dst, x);
+      fe_store(dst + NL, y);
+    }
+    // encoding for the challenge: y, sign of x; slot order pk_com, H, Gamma, R, Ok
+    uint32_t e[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) e[j] = yw[j];
+    if (te_x_sign(xw, T.sq.str.flags)) e[7] |= 0x80000000u;
+    const int slot = p == 0 ? 1 : p == 1 ? 2 : p == 2 ? 0 : p;
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+      if (q == slot) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) cp[q][j] = e[j];
+      }
+  }
+  challenge5<S>(c_out, cp, ad, ad_len, T.sq.str);
+  return valid;
+}
+
 // half 0: s*H - c*Gamma (4-table GLV Straus) ; half 1: -c*pk_com (2-table GLV Straus) + s*G + sb*B
 // (two fixed-base combs).  tabs: GLV table pairs of H, Gamma, pk_com.
 template <class S, int HALF>

@@ -116,7 +116,8 @@ struct ProveArgs {
 struct PedersenVerifyArgs {
   int suite;
   size_t n;
-  const uint8_t *h, *gamma, *pk_com, *r, *ok, *s, *sb;
+  const uint8_t *h, *gamma, *pk_com, *r, *ok, *s, *sb;   // affine_in: the five point arrays are 64-byte x || y
+  int affine_in;              // 0: compressed encodings; 1: x || y canonical; 2: x || y Montgomery-256
   uint32_t check_mask;        // CHK_INPUT | CHK_OUTPUT | CHK_PROOF
   BytesView ad;
   uint8_t* status;

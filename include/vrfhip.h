@@ -277,8 +277,9 @@ int32_t vrfhip_ietf_verify_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d
 
 /* The same verification for callers that hold the points in memory as arkworks `Affine { x, y }`
  * (the form `Public`, `Input`, `Output` wrap): pk_xy, input_xy, output_xy are n x 64 B, x || y as
- * 32-byte little-endian canonical integers.  No square roots are needed; InvalidData = coordinate
- * >= q or point off the curve. */
+ * 32-byte little-endian canonical integers (arkworks' Montgomery limbs under VRFHIP_FLAG_COORDS_MONT256).
+ * No square roots are needed; InvalidData = coordinate >= q, point off the curve, or (unless the context's
+ * VRFHIP_FLAG_PREVALIDATED_* bit for that point is set) point outside the prime-order subgroup. */
 /* `Input::new(alpha)` + `ietf::Verifier::verify` (src/lib.rs:14-16) in one call: what a deployed verifier holds is the
  * public key, the message alpha and the proof -- H is not on the wire, the verifier hashes alpha to the curve itself.  msg /
  * msg_off / msg_len name the messages as in vrfhip_ietf_prove_batch (n+1 offsets into msg, or msg_off = NULL and msg_len
@@ -381,6 +382,26 @@ int32_t vrfhip_pedersen_verify_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_
                                          const uint8_t* d_sb, const uint8_t* d_ad,
                                          const uint32_t* d_ad_off, uint32_t ad_len,
                                          uint8_t* d_status, void* stream);
+
+/* The same per-proof verification for callers that hold the five points in memory as arkworks `Affine { x, y }`
+ * (what `Input`, `Output` and `pedersen::Proof` wrap; replaces `pedersen::Verifier::verify`, src/lib.rs:14, on
+ * typed values): *_xy arrays are n x 64 B, x || y as 32-byte little-endian canonical integers (arkworks'
+ * Montgomery limbs under VRFHIP_FLAG_COORDS_MONT256; bandersnatch_sw: the Weierstrass coordinates; secp256r1:
+ * the affine P-256 coordinates); s, sb as above.  No square roots are needed.  Statuses are those of
+ * vrfhip_pedersen_verify_batch on the compressed encodings of the same points; InvalidData = coordinate >= q,
+ * point off the curve, point outside the prime-order subgroup (unless the context's VRFHIP_FLAG_PREVALIDATED_*
+ * bit for that point is set), or scalar >= r. */
+int32_t vrfhip_pedersen_verify_batch_affine(vrfhip_ctx* ctx, size_t n, const uint8_t* input_xy,
+                                            const uint8_t* output_xy, const uint8_t* pk_com_xy, const uint8_t* r_xy,
+                                            const uint8_t* ok_xy, const uint8_t* s, const uint8_t* sb,
+                                            const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
+                                            uint8_t* status);
+int32_t vrfhip_pedersen_verify_batch_affine_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_input_xy,
+                                                const uint8_t* d_output_xy, const uint8_t* d_pk_com_xy,
+                                                const uint8_t* d_r_xy, const uint8_t* d_ok_xy, const uint8_t* d_s,
+                                                const uint8_t* d_sb, const uint8_t* d_ad,
+                                                const uint32_t* d_ad_off, uint32_t ad_len,
+                                                uint8_t* d_status, void* stream);
 
 /* `pedersen::Verifier::verify` for a whole batch with ONE multi-scalar multiplication (random linear
  * combination).  With c_i recomputed from the proof's own points, the batch is
@@ -588,6 +609,21 @@ int32_t vrfhip_pedersen_verify_batch_multi(vrfhip_ctx* const* ctxs, int32_t n_ct
                                            const uint8_t* ok, const uint8_t* s, const uint8_t* sb, const uint8_t* ad,
                                            const uint32_t* ad_off, uint32_t ad_len, const uint8_t* rlc_seed,
                                            uint8_t* status);
+/* The x || y forms over n_ctx contexts: vrfhip_ietf_verify_batch_affine and (rlc_seed NULL)
+ * vrfhip_pedersen_verify_batch_affine or (rlc_seed non-NULL) vrfhip_pedersen_verify_batch_rlc_affine on each
+ * slice; points are n x 64 B as there.  What a typed Rust caller (`ietf::Verifier::verify`,
+ * `pedersen::Verifier::verify` on `Public` / `Input` / `Output` / `Proof` values, src/lib.rs:14-16) hands over
+ * without compressing a point.  All contexts must be of one suite (curve and suite id) and agree on
+ * VRFHIP_FLAG_COORDS_MONT256: VRFHIP_ERR_BAD_ARG otherwise. */
+int32_t vrfhip_ietf_verify_batch_affine_multi(vrfhip_ctx* const* ctxs, int32_t n_ctx, size_t n, const uint8_t* pk_xy,
+                                              const uint8_t* input_xy, const uint8_t* output_xy, const uint8_t* c,
+                                              const uint8_t* s, const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
+                                              uint8_t* status);
+int32_t vrfhip_pedersen_verify_batch_affine_multi(vrfhip_ctx* const* ctxs, int32_t n_ctx, size_t n, const uint8_t* input_xy,
+                                                  const uint8_t* output_xy, const uint8_t* pk_com_xy, const uint8_t* r_xy,
+                                                  const uint8_t* ok_xy, const uint8_t* s, const uint8_t* sb, const uint8_t* ad,
+                                                  const uint32_t* ad_off, uint32_t ad_len, const uint8_t* rlc_seed,
+                                                  uint8_t* status);
 
 /* Test-only primitives: the pieces under the batch calls, on their own, host pointers.
  * point_add: out[i] = a[i] + b[i] (`AffinePoint` addition, ark_ec TE group law; src/lib.rs:15), compressed points,

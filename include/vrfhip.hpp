@@ -27,6 +27,8 @@
 // Batch forms (what the GPU is for) take std::vector of the same types: ietf::verify_batch, ietf::prove_batch,
 // pedersen::verify_batch (single-MSM random-linear-combination path with automatic per-proof fallback),
 // KeySet + ietf::verify_batch_keyed (public keys with HBM-resident fixed-base tables).
+// Typed callers holding affine points (utils::XY) verify without compression: ietf::verify / verify_batch /
+// verify_batch_sharded over ietf::ItemXY, pedersen::verify / verify_batch / verify_batch_sharded over pedersen::ItemXY.
 #ifndef VRFHIP_HPP
 #define VRFHIP_HPP
 
@@ -472,6 +474,147 @@ std::vector<std::optional<XY>> te_to_sw(const Context<S>& ctx, const std::vector
 template <class S>
 std::vector<std::optional<XY>> sw_to_te(const Context<S>& ctx, const std::vector<XY>& pts) { return detail::te_sw_map(ctx, pts, 1); }
 }  // namespace utils
+
+// ------------------------------------------------------- verification from affine points (typed `Public`, `Input`, `Output`)
+// A caller holding arkworks values has the points as `Affine { x, y }`: utils::XY, x || y as 32-byte little-endian canonical
+// integers (arkworks' in-memory Montgomery limbs on a context with VRFHIP_FLAG_COORDS_MONT256; bandersnatch_sw: the
+// Weierstrass coordinates).  No point is compressed on the host and none is decompressed on the GPU; the statuses are those
+// of the encoded forms above.  The *_sharded forms take one context per GPU (vrfhip_*_verify_batch_affine_multi: the
+// contexts must share the suite and COORDS_MONT256).
+namespace ietf {
+template <class S>
+struct ItemXY { utils::XY pub, input, output; Proof<S> proof; };
+
+namespace detail_xy {
+template <class S>
+void columns(const std::vector<ItemXY<S>>& items, Bytes& pts, Bytes& cs) {      // pk | H | Gamma (64 B each), c | s
+  const size_t n = items.size();
+  pts.assign(3 * 64 * n + 1, 0);
+  cs.assign(2 * 32 * n + 1, 0);
+  for (size_t i = 0; i < n; ++i) {
+    const ItemXY<S>& t = items[i];
+    std::memcpy(pts.data() + 64 * i, t.pub.data(), 64);
+    std::memcpy(pts.data() + 64 * (n + i), t.input.data(), 64);
+    std::memcpy(pts.data() + 64 * (2 * n + i), t.output.data(), 64);
+    std::memcpy(cs.data() + 32 * i, t.proof.c.data(), 32);
+    std::memcpy(cs.data() + 32 * (n + i), t.proof.s.data(), 32);
+  }
+}
+}  // namespace detail_xy
+
+// `ietf::Verifier::verify` on affine points
+template <class S>
+Result verify(const Context<S>& ctx, const utils::XY& pub, const utils::XY& in, const utils::XY& out, const Bytes& ad,
+              const Proof<S>& p) {
+  uint8_t st = 0;
+  check(vrfhip_ietf_verify_batch_affine(ctx.handle(), 1, pub.data(), in.data(), out.data(), p.c.data(), p.s.data(),
+                                        detail::ad_ptr(ad), nullptr, (uint32_t)ad.size(), &st),
+        "vrfhip_ietf_verify_batch_affine");
+  return result_of(st);
+}
+// n x verify on affine points, one context
+template <class S>
+std::vector<Result> verify_batch(const Context<S>& ctx, const std::vector<ItemXY<S>>& items, const Bytes& ad) {
+  const size_t n = items.size();
+  Bytes pts, cs, st(n + 1);
+  detail_xy::columns(items, pts, cs);
+  const uint8_t* p = pts.data();
+  check(vrfhip_ietf_verify_batch_affine(ctx.handle(), n, p, p + 64 * n, p + 128 * n, cs.data(), cs.data() + 32 * n,
+                                        detail::ad_ptr(ad), nullptr, (uint32_t)ad.size(), st.data()),
+        "vrfhip_ietf_verify_batch_affine");
+  std::vector<Result> r(n);
+  for (size_t i = 0; i < n; ++i) r[i] = result_of(st[i]);
+  return r;
+}
+// n x verify on affine points over several contexts (one call: vrfhip_ietf_verify_batch_affine_multi)
+template <class S>
+std::vector<Result> verify_batch_sharded(const std::vector<const Context<S>*>& ctxs, const std::vector<ItemXY<S>>& items,
+                                         const Bytes& ad) {
+  const size_t n = items.size();
+  if (ctxs.empty()) throw std::invalid_argument("verify_batch_sharded: no context");
+  std::vector<vrfhip_ctx*> hs;
+  for (const Context<S>* c : ctxs) hs.push_back(c->handle());
+  Bytes pts, cs, st(n + 1);
+  detail_xy::columns(items, pts, cs);
+  const uint8_t* p = pts.data();
+  check(vrfhip_ietf_verify_batch_affine_multi(hs.data(), (int32_t)hs.size(), n, p, p + 64 * n, p + 128 * n, cs.data(),
+                                              cs.data() + 32 * n, detail::ad_ptr(ad), nullptr, (uint32_t)ad.size(),
+                                              st.data()), "vrfhip_ietf_verify_batch_affine_multi");
+  std::vector<Result> r(n);
+  for (size_t i = 0; i < n; ++i) r[i] = result_of(st[i]);
+  return r;
+}
+}  // namespace ietf
+
+namespace pedersen {
+template <class S> struct ProofXY { utils::XY pk_com, r, ok; Scalar s, sb; };
+template <class S> struct ItemXY { utils::XY input, output; ProofXY<S> proof; };
+
+namespace detail_xy {
+template <class S>
+void columns(const std::vector<ItemXY<S>>& items, Bytes& pts, Bytes& ss) {      // H | Gamma | pk_com | R | Ok, s | sb
+  const size_t n = items.size();
+  pts.assign(5 * 64 * n + 1, 0);
+  ss.assign(2 * 32 * n + 1, 0);
+  for (size_t i = 0; i < n; ++i) {
+    const ItemXY<S>& t = items[i];
+    const utils::XY* src[5] = {&t.input, &t.output, &t.proof.pk_com, &t.proof.r, &t.proof.ok};
+    for (size_t k = 0; k < 5; ++k) std::memcpy(pts.data() + 64 * (k * n + i), src[k]->data(), 64);
+    std::memcpy(ss.data() + 32 * i, t.proof.s.data(), 32);
+    std::memcpy(ss.data() + 32 * (n + i), t.proof.sb.data(), 32);
+  }
+}
+}  // namespace detail_xy
+
+// `pedersen::Verifier::verify` on affine points
+template <class S>
+Result verify(const Context<S>& ctx, const utils::XY& in, const utils::XY& out, const Bytes& ad, const ProofXY<S>& p) {
+  uint8_t st = 0;
+  check(vrfhip_pedersen_verify_batch_affine(ctx.handle(), 1, in.data(), out.data(), p.pk_com.data(), p.r.data(), p.ok.data(),
+                                            p.s.data(), p.sb.data(), detail::ad_ptr(ad), nullptr, (uint32_t)ad.size(), &st),
+        "vrfhip_pedersen_verify_batch_affine");
+  return result_of(st);
+}
+// n x verify on affine points, per proof, one context
+template <class S>
+std::vector<Result> verify_batch(const Context<S>& ctx, const std::vector<ItemXY<S>>& items, const Bytes& ad) {
+  const size_t n = items.size();
+  Bytes pts, ss, st(n + 1);
+  detail_xy::columns(items, pts, ss);
+  const uint8_t* p = pts.data();
+  check(vrfhip_pedersen_verify_batch_affine(ctx.handle(), n, p, p + 64 * n, p + 128 * n, p + 192 * n, p + 256 * n, ss.data(),
+                                            ss.data() + 32 * n, detail::ad_ptr(ad), nullptr, (uint32_t)ad.size(), st.data()),
+        "vrfhip_pedersen_verify_batch_affine");
+  std::vector<Result> r(n);
+  for (size_t i = 0; i < n; ++i) r[i] = result_of(st[i]);
+  return r;
+}
+// n x verify on affine points over several contexts (vrfhip_pedersen_verify_batch_affine_multi).  batched: one
+// multi-scalar multiplication per context with the per-proof fallback, as verify_batch on encoded points
+template <class S>
+std::vector<Result> verify_batch_sharded(const std::vector<const Context<S>*>& ctxs, const std::vector<ItemXY<S>>& items,
+                                         const Bytes& ad, bool batched = false) {
+  const size_t n = items.size();
+  if (ctxs.empty()) throw std::invalid_argument("verify_batch_sharded: no context");
+  std::vector<vrfhip_ctx*> hs;
+  for (const Context<S>* c : ctxs) hs.push_back(c->handle());
+  Bytes pts, ss, st(n + 1);
+  detail_xy::columns(items, pts, ss);
+  std::array<uint8_t, 32> seed;
+  if (batched) {
+    std::random_device rd;                                 // must be unpredictable to the provers
+    for (auto& b : seed) b = (uint8_t)rd();
+  }
+  const uint8_t* p = pts.data();
+  check(vrfhip_pedersen_verify_batch_affine_multi(hs.data(), (int32_t)hs.size(), n, p, p + 64 * n, p + 128 * n, p + 192 * n,
+                                                  p + 256 * n, ss.data(), ss.data() + 32 * n, detail::ad_ptr(ad), nullptr,
+                                                  (uint32_t)ad.size(), batched ? seed.data() : nullptr, st.data()),
+        "vrfhip_pedersen_verify_batch_affine_multi");
+  std::vector<Result> r(n);
+  for (size_t i = 0; i < n; ++i) r[i] = result_of(st[i]);
+  return r;
+}
+}  // namespace pedersen
 
 }  // namespace ark_vrf_hip
 #endif  // VRFHIP_HPP

@@ -122,6 +122,15 @@ fn affine_xy<S: Suite>(p: &AffinePoint<S>, out: &mut [u8; 64]) {
     p.y.serialize_uncompressed(&mut out[32..]).expect("32-byte base field");
 }
 
+/// Point `i` of the `k`-th of the point arrays of an `n`-item batch, as x || y (`affine_xy`), written straight into the
+/// batch's one pre-sized buffer: no compression, no allocation per point.  The library verifies these without a square
+/// root (`vrfhip_*_verify_batch_affine_multi`).  A short-Weierstrass point at infinity has no x || y form: it is written
+/// as (0, 0), which is not on the curve, and its item is reported InvalidData.
+fn put_xy<S: Suite>(buf: &mut [u8], n: usize, k: usize, i: usize, p: &AffinePoint<S>) {
+    let at = (k * n + i) * 64;
+    affine_xy::<S>(p, <&mut [u8; 64]>::try_from(&mut buf[at..at + 64]).expect("64-byte slot"));
+}
+
 fn point32<S: Suite>(p: &AffinePoint<S>, out: &mut [u8]) {
     let mut buf = Vec::with_capacity(32);
     codec::point_encode::<S>(p, &mut buf);
@@ -228,27 +237,21 @@ impl<S: GpuSuite> GpuBatch<S> {
     ) -> Result<Vec<Result<(), Error>>, GpuError> {
         let n = publics.len();
         assert!(n == inputs.len() && n == outputs.len() && n == proofs.len());
-        let mut buf = vec![0u8; 5 * n * 32];
-        {
-            let (pk, rest) = buf.split_at_mut(n * 32);
-            let (h, rest) = rest.split_at_mut(n * 32);
-            let (g, rest) = rest.split_at_mut(n * 32);
-            let (c, s) = rest.split_at_mut(n * 32);
-            for i in 0..n {
-                let r = i * 32..(i + 1) * 32;
-                point32::<S>(&publics[i].0, &mut pk[r.clone()]);
-                point32::<S>(&inputs[i].0, &mut h[r.clone()]);
-                point32::<S>(&outputs[i].0, &mut g[r.clone()]);
-                scalar32::<S>(&proofs[i].c, &mut c[r.clone()]);
-                scalar32::<S>(&proofs[i].s, &mut s[r]);
-            }
+        let mut pts = vec![0u8; 3 * n * 64]; // pk | h | gamma, x || y
+        let mut sc = vec![0u8; 2 * n * 32]; // c | s
+        for i in 0..n {
+            put_xy::<S>(&mut pts, n, 0, i, &publics[i].0);
+            put_xy::<S>(&mut pts, n, 1, i, &inputs[i].0);
+            put_xy::<S>(&mut pts, n, 2, i, &outputs[i].0);
+            scalar32::<S>(&proofs[i].c, &mut sc[i * 32..(i + 1) * 32]);
+            scalar32::<S>(&proofs[i].s, &mut sc[(n + i) * 32..(n + i + 1) * 32]);
         }
         let mut status = vec![0u8; n];
-        let p = buf.as_ptr();
+        let (p, q) = (pts.as_ptr(), sc.as_ptr());
         check(unsafe {
-            ffi::vrfhip_ietf_verify_batch_multi(
-                self.ctxs.as_ptr(), self.ctxs.len() as i32, n, p, p.add(n * 32), p.add(2 * n * 32), p.add(3 * n * 32),
-                p.add(4 * n * 32), ad.as_ptr(), core::ptr::null(), ad.len() as u32, status.as_mut_ptr(),
+            ffi::vrfhip_ietf_verify_batch_affine_multi(
+                self.ctxs.as_ptr(), self.ctxs.len() as i32, n, p, p.add(n * 64), p.add(2 * n * 64), q, q.add(n * 32),
+                ad.as_ptr(), core::ptr::null(), ad.len() as u32, status.as_mut_ptr(),
             )
         })?;
         Ok(status.into_iter().map(status_to_result).collect())
@@ -351,25 +354,25 @@ impl<S: GpuSuite> GpuBatch<S> {
     ) -> Result<Vec<Result<(), Error>>, GpuError> {
         let n = inputs.len();
         assert!(n == outputs.len() && n == proofs.len());
-        let mut buf = vec![0u8; 7 * n * 32]; // h | gamma | pk_com | r | ok | s | sb
+        let mut pts = vec![0u8; 5 * n * 64]; // h | gamma | pk_com | r | ok, x || y
+        let mut sc = vec![0u8; 2 * n * 32]; // s | sb
         for i in 0..n {
-            let at = |k: usize| (k * n + i) * 32..(k * n + i + 1) * 32;
-            point32::<S>(&inputs[i].0, &mut buf[at(0)]);
-            point32::<S>(&outputs[i].0, &mut buf[at(1)]);
-            point32::<S>(&proofs[i].pk_com, &mut buf[at(2)]);
-            point32::<S>(&proofs[i].r, &mut buf[at(3)]);
-            point32::<S>(&proofs[i].ok, &mut buf[at(4)]);
-            scalar32::<S>(&proofs[i].s, &mut buf[at(5)]);
-            scalar32::<S>(&proofs[i].sb, &mut buf[at(6)]);
+            put_xy::<S>(&mut pts, n, 0, i, &inputs[i].0);
+            put_xy::<S>(&mut pts, n, 1, i, &outputs[i].0);
+            put_xy::<S>(&mut pts, n, 2, i, &proofs[i].pk_com);
+            put_xy::<S>(&mut pts, n, 3, i, &proofs[i].r);
+            put_xy::<S>(&mut pts, n, 4, i, &proofs[i].ok);
+            scalar32::<S>(&proofs[i].s, &mut sc[i * 32..(i + 1) * 32]);
+            scalar32::<S>(&proofs[i].sb, &mut sc[(n + i) * 32..(n + i + 1) * 32]);
         }
         let mut status = vec![0u8; n];
-        let p = buf.as_ptr();
+        let (p, q) = (pts.as_ptr(), sc.as_ptr());
         let seed = batched_seed.map_or(core::ptr::null(), |s| s.as_ptr());
         check(unsafe {
-            ffi::vrfhip_pedersen_verify_batch_multi(
-                self.ctxs.as_ptr(), self.ctxs.len() as i32, n, p, p.add(n * 32), p.add(2 * n * 32), p.add(3 * n * 32),
-                p.add(4 * n * 32), p.add(5 * n * 32), p.add(6 * n * 32), ad.as_ptr(), core::ptr::null(),
-                ad.len() as u32, seed, status.as_mut_ptr(),
+            ffi::vrfhip_pedersen_verify_batch_affine_multi(
+                self.ctxs.as_ptr(), self.ctxs.len() as i32, n, p, p.add(n * 64), p.add(2 * n * 64), p.add(3 * n * 64),
+                p.add(4 * n * 64), q, q.add(n * 32), ad.as_ptr(), core::ptr::null(), ad.len() as u32, seed,
+                status.as_mut_ptr(),
             )
         })?;
         Ok(status.into_iter().map(status_to_result).collect())
@@ -519,19 +522,20 @@ impl GpuBatchSec1 {
     ) -> Result<Vec<Result<(), Error>>, GpuError> {
         let n = publics.len();
         assert!(n == inputs.len() && n == outputs.len() && n == proofs.len());
-        let (mut pk, mut h, mut g) = (vec![0u8; n * SEC1], vec![0u8; n * SEC1], vec![0u8; n * SEC1]);
-        let (mut c, mut s) = (vec![0u8; n * 32], vec![0u8; n * 32]);
+        let mut pts = vec![0u8; 3 * n * 64]; // pk | h | gamma, x || y (little-endian)
+        let mut sc = vec![0u8; 2 * n * 32]; // c | s
         for i in 0..n {
-            Self::put_point(&publics[i].0, &mut pk[i * SEC1..(i + 1) * SEC1]);
-            Self::put_point(&inputs[i].0, &mut h[i * SEC1..(i + 1) * SEC1]);
-            Self::put_point(&outputs[i].0, &mut g[i * SEC1..(i + 1) * SEC1]);
-            Self::put_scalar(&proofs[i].c, &mut c[i * 32..(i + 1) * 32]);
-            Self::put_scalar(&proofs[i].s, &mut s[i * 32..(i + 1) * 32]);
+            put_xy::<P256>(&mut pts, n, 0, i, &publics[i].0);
+            put_xy::<P256>(&mut pts, n, 1, i, &inputs[i].0);
+            put_xy::<P256>(&mut pts, n, 2, i, &outputs[i].0);
+            Self::put_scalar(&proofs[i].c, &mut sc[i * 32..(i + 1) * 32]);
+            Self::put_scalar(&proofs[i].s, &mut sc[(n + i) * 32..(n + i + 1) * 32]);
         }
         let mut status = vec![0u8; n];
+        let (p, q) = (pts.as_ptr(), sc.as_ptr());
         check(unsafe {
-            ffi::vrfhip_ietf_verify_batch_multi(
-                self.ctxs.as_ptr(), self.ctxs.len() as i32, n, pk.as_ptr(), h.as_ptr(), g.as_ptr(), c.as_ptr(), s.as_ptr(),
+            ffi::vrfhip_ietf_verify_batch_affine_multi(
+                self.ctxs.as_ptr(), self.ctxs.len() as i32, n, p, p.add(n * 64), p.add(2 * n * 64), q, q.add(n * 32),
                 ad.as_ptr(), core::ptr::null(), ad.len() as u32, status.as_mut_ptr(),
             )
         })?;
@@ -628,24 +632,23 @@ impl GpuBatchSec1 {
     ) -> Result<Vec<Result<(), Error>>, GpuError> {
         let n = inputs.len();
         assert!(n == outputs.len() && n == proofs.len());
-        let mut pts = vec![0u8; 5 * n * SEC1]; // h | gamma | pk_com | r | ok
+        let mut pts = vec![0u8; 5 * n * 64]; // h | gamma | pk_com | r | ok, x || y (little-endian)
         let mut sc = vec![0u8; 2 * n * 32]; // s | sb
         for i in 0..n {
-            let at = |k: usize| (k * n + i) * SEC1..(k * n + i + 1) * SEC1;
-            Self::put_point(&inputs[i].0, &mut pts[at(0)]);
-            Self::put_point(&outputs[i].0, &mut pts[at(1)]);
-            Self::put_point(&proofs[i].pk_com, &mut pts[at(2)]);
-            Self::put_point(&proofs[i].r, &mut pts[at(3)]);
-            Self::put_point(&proofs[i].ok, &mut pts[at(4)]);
+            put_xy::<P256>(&mut pts, n, 0, i, &inputs[i].0);
+            put_xy::<P256>(&mut pts, n, 1, i, &outputs[i].0);
+            put_xy::<P256>(&mut pts, n, 2, i, &proofs[i].pk_com);
+            put_xy::<P256>(&mut pts, n, 3, i, &proofs[i].r);
+            put_xy::<P256>(&mut pts, n, 4, i, &proofs[i].ok);
             Self::put_scalar(&proofs[i].s, &mut sc[i * 32..(i + 1) * 32]);
             Self::put_scalar(&proofs[i].sb, &mut sc[(n + i) * 32..(n + i + 1) * 32]);
         }
         let mut status = vec![0u8; n];
         let (p, q) = (pts.as_ptr(), sc.as_ptr());
         check(unsafe {
-            ffi::vrfhip_pedersen_verify_batch_multi(
-                self.ctxs.as_ptr(), self.ctxs.len() as i32, n, p, p.add(n * SEC1), p.add(2 * n * SEC1), p.add(3 * n * SEC1),
-                p.add(4 * n * SEC1), q, q.add(n * 32), ad.as_ptr(), core::ptr::null(), ad.len() as u32, core::ptr::null(),
+            ffi::vrfhip_pedersen_verify_batch_affine_multi(
+                self.ctxs.as_ptr(), self.ctxs.len() as i32, n, p, p.add(n * 64), p.add(2 * n * 64), p.add(3 * n * 64),
+                p.add(4 * n * 64), q, q.add(n * 32), ad.as_ptr(), core::ptr::null(), ad.len() as u32, core::ptr::null(),
                 status.as_mut_ptr(),
             )
         })?;
@@ -777,19 +780,20 @@ impl GpuBatchSw {
     ) -> Result<Vec<Result<(), Error>>, GpuError> {
         let n = publics.len();
         assert!(n == inputs.len() && n == outputs.len() && n == proofs.len());
-        let (mut pk, mut h, mut g) = (vec![0u8; n * SWPT], vec![0u8; n * SWPT], vec![0u8; n * SWPT]);
-        let (mut c, mut s) = (vec![0u8; n * 32], vec![0u8; n * 32]);
+        let mut pts = vec![0u8; 3 * n * 64]; // pk | h | gamma, x || y (the Weierstrass coordinates)
+        let mut sc = vec![0u8; 2 * n * 32]; // c | s
         for i in 0..n {
-            Self::put_point(&publics[i].0, &mut pk[i * SWPT..(i + 1) * SWPT]);
-            Self::put_point(&inputs[i].0, &mut h[i * SWPT..(i + 1) * SWPT]);
-            Self::put_point(&outputs[i].0, &mut g[i * SWPT..(i + 1) * SWPT]);
-            scalar32::<BSw>(&proofs[i].c, &mut c[i * 32..(i + 1) * 32]);
-            scalar32::<BSw>(&proofs[i].s, &mut s[i * 32..(i + 1) * 32]);
+            put_xy::<BSw>(&mut pts, n, 0, i, &publics[i].0);
+            put_xy::<BSw>(&mut pts, n, 1, i, &inputs[i].0);
+            put_xy::<BSw>(&mut pts, n, 2, i, &outputs[i].0);
+            scalar32::<BSw>(&proofs[i].c, &mut sc[i * 32..(i + 1) * 32]);
+            scalar32::<BSw>(&proofs[i].s, &mut sc[(n + i) * 32..(n + i + 1) * 32]);
         }
         let mut status = vec![0u8; n];
+        let (p, q) = (pts.as_ptr(), sc.as_ptr());
         check(unsafe {
-            ffi::vrfhip_ietf_verify_batch_multi(
-                self.ctxs.as_ptr(), self.ctxs.len() as i32, n, pk.as_ptr(), h.as_ptr(), g.as_ptr(), c.as_ptr(), s.as_ptr(),
+            ffi::vrfhip_ietf_verify_batch_affine_multi(
+                self.ctxs.as_ptr(), self.ctxs.len() as i32, n, p, p.add(n * 64), p.add(2 * n * 64), q, q.add(n * 32),
                 ad.as_ptr(), core::ptr::null(), ad.len() as u32, status.as_mut_ptr(),
             )
         })?;
