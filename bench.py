@@ -13,10 +13,13 @@ parent touches no GPU: it only spawns `python -m torch.distributed.run ... bench
 N > 1: one process per GPU over RCCL; every rank works on its own 2^20 items (weak scaling); the only
 collective is the gather of the result bytes.
 
-The JSON line also carries, under "configs", the other BASELINE.json configurations measured in the same run
-(IETF prove 2^16; Pedersen prove + verify on JubJub 2^20, per proof and batched; pairing checks 2^14, per item
-and against a shared G2 pair), each with its own `roofline` (dominant kernel, HIP events on the launch stream)
-and, at N = 1, a `cpu_baseline` leg (the plain-C / Python oracle under oracle/, kind "port", bounded sample).
+A plain run does only what the headline needs: it makes the batch, warms up, times the steps, checks and (with
+--dump-outputs) writes the statuses, and prints the line.  With --full the JSON line also carries, under "configs",
+the other BASELINE.json configurations measured in the same run (IETF prove 2^16; Pedersen prove + verify on JubJub
+2^20, per proof and batched; pairing checks 2^14, per item and against a shared G2 pair), each with its own
+`roofline` (dominant kernel, HIP events on the launch stream) and, at N = 1, a `cpu_baseline` leg (the plain-C /
+Python oracle under oracle/, kind "port", bounded sample); the headline then also gets its pre-validated rate, its
+CPU baseline, the prove rate of its batch and, at N > 1, the other scaling mode.
 
 `roofline` prices the longest kernel against HBM as the contract asks; the path is VALU-integer bound, so
 `valu` gives the ceiling that matters: the fraction of the SIMDs' vector issue slots the kernel fills, from the
@@ -53,23 +56,30 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log2-batch", type=int, default=LOG2_BATCH)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="headline only (skip the other BASELINE.json configs)")
-    ap.add_argument("--config-steps", type=int, default=5, help="timed steps per secondary config")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the other BASELINE.json configs, the CPU "
+                         "baselines, the pre-validated headline, the prove rate and, at N > 1, the other scaling mode")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the other BASELINE.json configs")
+    ap.add_argument("--config-steps", type=int, default=None, help="with --full: timed steps per secondary config (5)")
     ap.add_argument("--prevalidated", action="store_true",
                     help="headline without the subgroup check (inputs declared validated by the caller)")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU time budget per cpu_baseline leg")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="with --full: CPU time budget per cpu_baseline leg (8)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="what `value` measures at N > 1: weak = 2^log2_batch items per GPU (global batch grows with N); strong = "
                          "ONE global batch of 2^log2_batch items cut into N contiguous shards (BASELINE.json: '2^20 ... sharded "
-                         "8x').  The other mode is measured in the same run and reported under `scaling_modes`.")
-    ap.add_argument("--only", default="", help="comma-separated secondary legs to run (default: all)")
+                         "8x').  With --full the other mode is measured in the same run; `scaling_modes` reports what was measured.")
+    ap.add_argument("--only", default="", help="with --full: comma-separated secondary legs to run (default: all)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the headline path returned in its last step (the verify "
                          "statuses of the whole batch) as DIR/<name>.npy in float32, for output-by-output comparison of builds")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full and (args.only or args.config_steps is not None or args.cpu_seconds is not None):
+        ap.error("--only, --config-steps and --cpu-seconds choose what --full measures: add --full")
+    args.config_steps = 5 if args.config_steps is None else args.config_steps
+    args.cpu_seconds = 8.0 if args.cpu_seconds is None else args.cpu_seconds
     return args
 
 
@@ -102,11 +112,9 @@ def self_launch(args):
 
 
 def synth_msgs(lo, n):
-    out = np.empty((n, 32), dtype=np.uint8)
     pre = b"vrfhip-msg"
-    for k in range(n):
-        out[k] = np.frombuffer(hashlib.sha512(pre + int(lo + k).to_bytes(8, "little")).digest()[:32], np.uint8)
-    return out
+    raw = b"".join(hashlib.sha512(pre + int(lo + k).to_bytes(8, "little")).digest()[:32] for k in range(n))
+    return np.frombuffer(raw, np.uint8).reshape(n, 32).copy()
 
 
 def forgery_kinds(first, m):
@@ -993,7 +1001,8 @@ def run_rank(args):
         b = {"sk": sk_, "msg": msg_, "gamma": mk_(), "c": mk_(), "s": mk_(), "pk": mk_(), "hh": mk_()}
         pst_ = torch.empty(m, dtype=torch.uint8, device=dev)
         best = 1e30
-        for _ in range(2):                              # the first call includes first-touch of the workspace
+        # the first call includes first-touch of the workspace: --full times a second one for proofs_per_sec
+        for _ in range(2 if args.full else 1):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             ctx.ietf_prove_batch_dev(sk_, msg_, 32, b["gamma"], b["c"], b["s"], b["pk"], b["hh"], pst_)
@@ -1026,18 +1035,18 @@ def run_rank(args):
 
     # weak: every rank its own 2^log2_batch items.  strong: ONE global batch of 2^log2_batch items, rank g verifies the
     # contiguous shard sharding.shard_range gives it (BASELINE.json configs: "2^20 ... sharded 8x").  At N = 1 they coincide.
+    # A plain run makes only the batch its headline verifies; --full also the other one (the other scaling mode; the
+    # prevalidated, CPU and secondary legs work on the rank's own 2^log2_batch items).
     from ark_ec_vrfs_amd.sharding import shard_range
-    weak = make_batch(lo, n)
     s_lo, s_hi = shard_range(n, rank, world)
-    strong = weak if world == 1 else make_batch(s_lo, s_hi - s_lo)
+    weak = make_batch(lo, n) if args.full or args.scaling == "weak" or world == 1 else None
+    strong = weak if world == 1 else make_batch(s_lo, s_hi - s_lo) if args.full or args.scaling == "strong" else None
     # the timed legs verify copies in which forgery_kinds' items are forged; the secondary legs keep the genuine proofs
-    weak_h = forged(weak, lo)
-    strong_h = weak_h if world == 1 else forged(strong, s_lo)
+    weak_h = forged(weak, lo) if weak is not None else None
+    strong_h = weak_h if world == 1 else forged(strong, s_lo) if strong is not None else None
     main_b, other_b = (strong_h, weak_h) if args.scaling == "strong" else (weak_h, strong_h)
     main_n = (s_hi - s_lo) if args.scaling == "strong" else n
     main_global = n if args.scaling == "strong" else world * n
-    sk, msg, gamma, c, s, pk, hh = (weak[k] for k in ("sk", "msg", "gamma", "c", "s", "pk", "hh"))
-    prove_s = weak["prove_s"]
 
     step = verify_step(main_b)
     for _ in range(args.warmup):
@@ -1055,7 +1064,7 @@ def run_rank(args):
     other = "weak" if args.scaling == "strong" else "strong"
     if world == 1:
         modes[other] = dict(modes[args.scaling])
-    else:
+    elif args.full:
         o_n = n if other == "weak" else (s_hi - s_lo)
         o_global = world * n if other == "weak" else n
         o_steps = max(3, args.config_steps)
@@ -1063,11 +1072,11 @@ def run_rank(args):
         check_statuses(full_o, o_global)
         modes[other] = {"value": o_global * o_steps / el_o, "ms_per_step": el_o / o_steps * 1e3, "global_batch": o_global,
                         "items_per_gpu": o_global // world, "steps": o_steps}
-    step = verify_step(weak_h)                       # the prevalidated leg: the rank's own 2^log2_batch items
 
     # the same batch with the points declared validated (typed Public/Input/Output values): round 1's operation
     preval = None
-    if can_check and not args.prevalidated:
+    if args.full and can_check and not args.prevalidated:
+        step = verify_step(weak_h)                   # the rank's own 2^log2_batch items
         ctx.set_prevalidated(True)
         el_p, full_p = timed(D, step, max(2, args.config_steps), 1, gather_t=weak_h["status"], n_per_rank=n)
         ctx.set_prevalidated(False)
@@ -1077,9 +1086,10 @@ def run_rank(args):
                   "value": world * n * max(2, args.config_steps) / el_p, "unit": "verifies/s",
                   "ms_per_step": el_p / max(2, args.config_steps) * 1e3}
 
-    want_cpu = (not args.no_cpu_baseline) and world == 1
+    want_cpu = args.full and (not args.no_cpu_baseline) and world == 1
     configs = {}
-    if not args.no_configs:
+    if args.full and not args.no_configs:
+        sk, msg, gamma, c, s, pk, hh = (weak[k] for k in ("sk", "msg", "gamma", "c", "s", "pk", "hh"))
         from ark_ec_vrfs_amd import BabyJubJubSha512Tai, BandersnatchSwSha512Tai, Ed25519Sha512Tai, Secp256r1Sha256Tai
         legs = (("ietf_prove", lambda: {"ietf_prove": cfg_ietf_prove(D, args, ctx, sk, msg, want_cpu and rank == 0)}),
                 ("shard_sizes", lambda: cfg_shard_sizes(D, args, ctx, pk, hh, gamma, c, s)),
@@ -1130,12 +1140,13 @@ def run_rank(args):
             "roofline": r, "valu": v, "pmc_stale": pmc_table()[1],
             "stage_ms_per_step": {"decode": stage_ms[0], "straus_v": stage_ms[1], "straus_u": stage_ms[2],
                                   "finish": stage_ms[3]},
-            "proofs_per_sec": n / prove_s,
         }
+        if args.full:
+            out["proofs_per_sec"] = n / weak["prove_s"]
         if preval:
             out["prevalidated"] = preval
         if want_cpu:
-            out["cpu_baseline"] = headline_cpu_baseline(args, pk, hh, weak_h["gamma"], weak_h["c"], weak_h["s"], weak_h["status"])
+            out["cpu_baseline"] = headline_cpu_baseline(args, weak["pk"], weak["hh"], weak_h["gamma"], weak_h["c"], weak_h["s"], weak_h["status"])
         if configs:
             out["configs"] = configs
         print_result(out, configs, world)

@@ -242,3 +242,54 @@ def test_bench_times_the_asked_steps_and_dumps_the_last_one(tmp_path):
     b = _load_bench()
     want = b.expected_status(b.forgery_kinds(0, 1 << 12))
     assert st.dtype == np.float32 and st.shape == (1 << 12,) and (st == want).all() and set(np.unique(st)) == {0, 1, 2}
+
+
+def test_full_only_options_need_full_and_reach_the_ranks():
+    """--only, --config-steps and --cpu-seconds only shape what --full measures: without --full they are refused rather
+    than ignored.  --full itself is passed through to the ranks like every other flag."""
+    for extra in (["--only", "pairing"], ["--config-steps", "2"], ["--cpu-seconds", "1"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True,
+                             timeout=60)
+        assert out.returncode == 2 and "--full" in out.stderr, extra
+    env = dict(os.environ, VRFHIP_BENCH_DRYRUN="1")
+    env.pop("WORLD_SIZE", None)
+    argv = ["--gpus", "2", "--full", "--only", "pairing", "--config-steps", "2"]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, env=env, capture_output=True, text=True,
+                         timeout=60)
+    assert out.returncode == 0, out.stderr
+    cmd = json.loads(out.stdout.strip().splitlines()[-1])["launch"]
+    assert cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:] == argv
+
+
+def test_synthetic_messages_are_the_oracles():
+    """The headline's messages: msg_i = SHA512("vrfhip-msg" || u64_le(i))[..32], row by row."""
+    from oracle import vrf_oracle as o
+    b = _load_bench()
+    for lo, m in ((0, 5), (1 << 20, 3), (12345, 1)):
+        got = b.synth_msgs(lo, m)
+        assert got.shape == (m, 32) and got.dtype == np.uint8 and got.flags.writeable
+        assert [r.tobytes() for r in got] == [o.synth_msg(lo + k) for k in range(m)]
+
+
+@pytest.mark.gpu
+def test_plain_run_measures_the_headline_alone_and_full_adds_the_rest(tmp_path):
+    """A plain run prints the headline line only: no secondary legs, CPU baseline, pre-validated rate or prove rate.  The
+    same command with --full (one secondary leg, a short CPU budget) carries them again."""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--log2-batch", "12"]
+    env = dict(os.environ, VRFHIP_BENCH_CONFIGS_FILE=str(tmp_path / "configs.json"))
+    out = subprocess.run(base, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-4000:]
+    assert "bench_configs" not in out.stdout and not (tmp_path / "configs.json").exists()
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["configs_summary"] == {}
+    for k in ("cpu_baseline", "prevalidated", "proofs_per_sec"):
+        assert k not in d, k
+    out = subprocess.run(base + ["--full", "--only", "from_alpha", "--config-steps", "2", "--cpu-seconds", "0.2"], env=env,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-4000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["configs_summary"]["ietf_verify_from_alpha"][0] > 0
+    assert d["cpu_baseline"]["kind"] == "port" and d["prevalidated"]["value"] > 0 and d["proofs_per_sec"] > 0
+    assert json.load(open(tmp_path / "configs.json"))["configs"]["ietf_verify_from_alpha"]["value"] > 0

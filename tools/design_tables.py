@@ -1,6 +1,6 @@
 """Prints the two measurement tables of DESIGN.md section 4 from the committed round-4 records, so that the document quotes
 the committed run, not a remembered one:
-  profiles/r04/bench_n1_default.json            the default `python bench.py` line (one MI355X)
+  profiles/r04/bench_n1_default.json            the `python bench.py --full` line (one MI355X)
   profiles/r04/rocprofv3_kernels_by_grid.json   per-kernel counters of the profiled bench (tools/profile_round4.sh)
 usage: python tools/design_tables.py  > /tmp/tables.md"""
 import json, os

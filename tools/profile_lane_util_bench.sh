@@ -1,11 +1,11 @@
-# Active lanes per vector instruction of EVERY kernel of the default bench command:
+# Active lanes per vector instruction of EVERY kernel of the full bench command:
 # SQ_THREAD_CYCLES_VALU / SQ_INSTS_VALU (64 = no lane ever idle).  usage (GPU box): bash tools/profile_lane_util_bench.sh
 set -e
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/lane_util_bench
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 560 rocprofv3 --pmc SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU --kernel-trace --output-format csv -d $O -o run -- python3 $R/bench.py --steps 2 --warmup 1 --config-steps 1 --no-cpu-baseline > $O/run.log 2>&1; echo pmc_ok
+timeout -k 10 560 rocprofv3 --pmc SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU --kernel-trace --output-format csv -d $O -o run -- python3 $R/bench.py --full --steps 2 --warmup 1 --config-steps 1 --no-cpu-baseline > $O/run.log 2>&1; echo pmc_ok
 python3 - <<PY
 import csv, collections, glob, re
 f = glob.glob("$O/**/*counter_collection.csv", recursive=True)[0]

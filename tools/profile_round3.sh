@@ -1,4 +1,4 @@
-# Round-3 profiling: rocprofv3 passes over ONE command -- the default bench (headline + every BASELINE config and the
+# Round-3 profiling: rocprofv3 passes over ONE command -- the full bench (headline + every BASELINE config and the
 # Ed25519 / Baby-JubJub / secp256r1 legs in the same process).  Kernel trace + stats first, then one --pmc group per pass (the guide's
 # HBM recipe: FETCH_SIZE and WRITE_SIZE in separate passes).  Raw output under gpurun_out/r03prof/;
 # tools/summarize_profiles3.py condenses it into profiles/r03/ and profiles/pmc_kernels.json.
@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r03prof
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 3 --warmup 1 --config-steps 2 --no-cpu-baseline"
+B="python3 $R/bench.py --full --steps 3 --warmup 1 --config-steps 2 --no-cpu-baseline"
 timeout -k 10 560 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- $B > $O/stats.log 2>&1; echo stats_ok
 timeout -k 10 560 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/sq -o run -- $B > $O/sq.log 2>&1; echo sq_ok
 timeout -k 10 560 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o run -- $B > $O/fetch.log 2>&1; echo fetch_ok

@@ -87,7 +87,7 @@ for e in table.values():
             n64 = e["SQ_INSTS_VALU_INT64"]
             e["issue_cycle_frac"] = (n64 * 4.0 + max(e["SQ_INSTS_VALU"] - n64, 0.0) * 2.0) / (cycles * 1024.0)
 rows = sorted(table.values(), key=lambda e: -e.get("avg_duration_ns", 0) * e.get("launches", 1))
-json.dump({"command": "rocprofv3 {--kernel-trace --stats | --pmc <one group per pass> --kernel-trace} -- python3 bench.py --steps 3 "
+json.dump({"command": "rocprofv3 {--kernel-trace --stats | --pmc <one group per pass> --kernel-trace} -- python3 bench.py --full --steps 3 "
                       "--warmup 1 --config-steps 2 --no-cpu-baseline  (tools/profile_round3.sh)",
            "passes": ["SQ_INSTS_VALU SQ_WAVES GRBM_GUI_ACTIVE", "FETCH_SIZE", "WRITE_SIZE",
                       "SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_INT32 SQ_INSTS_SALU SQ_WAVE_CYCLES"],
