@@ -630,16 +630,24 @@ VRF_HD uint32_t fe_dlog2_low8(const Fe<L, V>& w_in, const SqrtTables& T) {
 //     g odd             : g += f                        (g / f) depends on g mod f only
 //     then              : g /= 2, eta -= 1              sign flips iff f = 3, 5 (mod 8)
 // The pair converges to f = g = gcd; the symbol is known once f = 1.  Every decision reads the low bits of f
-// and g and the counter eta only, so JAC_K = 29 steps run on the low 32-bit words (one VGPR each) and yield a
-// 2x2 matrix of non-negative 30-bit entries; applying it to the 9-limb numbers divides by 2^29 exactly, i.e.
-// drops one 29-bit limb.  The step is branch-free and every lane of a wave runs the same shape; 24..30 rounds
-// for 255-bit inputs (measured on 3e4 random values; a wave pays the maximum of its lanes, ~29).  ~1000 cheap
-// 32-bit VOP2 instructions + 36 multiply-adds per round: about a third of the exponentiation.
+// and g and the counter eta only, so a round of JAC_K = 29 steps runs on the low 32-bit words (one VGPR each) and
+// yields a 2x2 matrix of non-negative entries, each row summing to at most 2^29 (every step doubles the f row and
+// adds it to the g row at most once); applying it to the 9-limb numbers divides by 2^29 exactly, i.e. drops one
+// 29-bit limb, and the 64-bit column sums stay below 2 * 2^29 * 2^29 + carry < 2^60.  24..30 rounds for 255-bit
+// inputs (measured on 3e4 random values; a wave pays the maximum of its lanes, ~29).
+// The steps of a round run several at a time (jac_steps_var, libsecp256k1's variable-time "posdivsteps"): all
+// trailing zeros of g in one shift, then, with g odd and eta >= 0 after the swap, up to min(eta + 1, steps left, 4)
+// low bits of g cleared at once by g += f w, w = -g / f (mod 2^k).  eta + 1 bounds k because no swap can come
+// before eta turns negative, so the batch is the single steps' own sequence and the matrix, the sign and eta come
+// out identical.  ~9 iterations per lane and round, ~13 for the slowest lane of a wave of random inputs, against
+// 29 single steps, the 36 multiply-adds of the matrix product unchanged: 11 % fewer VALU instructions and 8 % less
+// time in the checked verify decode kernel (six symbols and half an inversion per proof), measured on MI355X.
 // chi(R) = chi(2)^261 = 1 because q = 1 (mod 8) for both Montgomery fields (and R = 1 for 2^255 - 19): the symbol of
 // the stored image is the symbol of the value.
 static_assert(vrfk::CHI_R == 1, "jacobi_limbs callers assume chi(R) = 1");
 constexpr int JAC_K = 29;
 constexpr int JAC_MAX_ROUNDS = 40;      // rounds needed: <= 30 in 3e4 samples, tail decays ~50x per round
+static_assert(JAC_K + 3 <= 32, "after JAC_K steps the low words must still hold the bits 1 and 2 that the sign reads");
 
 // wave-level "any lane" on the device, identity on the host build
 VRF_HD bool vrf_any(bool x) {
@@ -648,6 +656,57 @@ VRF_HD bool vrf_any(bool x) {
 #else
   return x;
 #endif
+}
+
+// The matrix of one round: 2^JAC_K (f', g') = (u f + v g, q f + r g).
+struct JacTrans { uint32_t u, v, q, r; };
+
+// JAC_K steps one at a time, branch-free and of fixed shape (the prover's constant-time inversion).
+VRF_HD int32_t jac_steps_ct(int32_t eta, uint32_t f, uint32_t g, JacTrans& t) {
+  uint32_t u = 1, v = 0, q = 0, r = 1;
+#pragma unroll
+  for (int i = 0; i < JAC_K; ++i) {
+    const uint32_t m = 0u - (g & 1u);                        // g odd
+    const uint32_t sw = m & (uint32_t)(eta >> 31);           // ... and eta < 0: swap
+    uint32_t x = (f ^ g) & sw; f ^= x; g ^= x;
+    x = (u ^ q) & sw; u ^= x; q ^= x;
+    x = (v ^ r) & sw; v ^= x; r ^= x;
+    eta = (eta ^ (int32_t)sw) - (int32_t)sw;
+    g += f & m; q += u & m; r += v & m;
+    g >>= 1; u <<= 1; v <<= 1; eta -= 1;
+  }
+  t = JacTrans{u, v, q, r};
+  return eta;
+}
+
+// `left` steps (JAC_K, or 0 for a lane that idles) several at a time, as described above; returns eta.  SIGN: bit 1
+// of `jac` follows the sign of the symbol.  The trip count varies per lane; a finished lane waits under the mask.
+// Every partial matrix is the single steps' matrix at some step, so no entry exceeds 2^JAC_K: u w and v w are the
+// f row after k more doublings and fit 32 bits like the rest.
+template <bool SIGN>
+VRF_HD int32_t jac_steps_var(int32_t eta, uint32_t f, uint32_t g, int left, JacTrans& t, uint32_t& jac) {
+  uint32_t u = 1, v = 0, q = 0, r = 1;
+  int i = left;
+#pragma unroll 1
+  for (;;) {
+    const int z = __builtin_ctz(g | (~0u << i));             // steps with g even, at most the i left (sentinel bit)
+    g >>= z; u <<= z; v <<= z; eta -= z; i -= z;
+    if (SIGN) jac ^= (f ^ (f >> 1)) & ((uint32_t)z << 1);  // (2 / f)^z: -1 iff f = 3, 5 (mod 8) and z odd
+    if (i == 0) break;
+    const bool sw = eta < 0;                                 // g odd: swap if eta < 0
+    if (SIGN) jac ^= sw ? f & g : 0u;
+    const uint32_t nf = sw ? g : f, ng = sw ? f : g, nu = sw ? q : u, nq = sw ? u : q, nv = sw ? r : v, nr = sw ? v : r;
+    f = nf; g = ng; u = nu; q = nq; v = nv; r = nr;
+    eta = sw ? -eta : eta;
+    int k = eta + 1 < i ? eta + 1 : i;
+    k = k < 4 ? k : 4;
+    // w = -g / f (mod 2^k): f (f^2 - 2) = -1 / f (mod 16); the operands are cut to 4 bits so the products are 24-bit ones
+    const uint32_t f4 = f & 15u, g4 = g & 15u;
+    const uint32_t w = (g4 * f4 * ((f4 * f4 + 14u) & 15u)) & ((1u << k) - 1u);
+    g += f * w; q += u * w; r += v * w;                      // clears the k low bits of g; the next shift takes them
+  }
+  t = JacTrans{u, v, q, r};
+  return eta;
 }
 
 // x: exact 29-bit limbs of an integer in [0, 2^256).  Returns +1 / -1, 0 if x = 0 (mod q), 2 if the rounds ran out.
@@ -663,22 +722,11 @@ VRF_HD int jacobi_limbs(const uint32_t x[NL]) {
 #pragma unroll 1
   for (int round = 0; round < JAC_MAX_ROUNDS; ++round) {
     if (!vrf_any(!done)) break;
-    uint32_t f0 = f[0] | (f[1] << LW), g0 = g[0] | (g[1] << LW);
-    uint32_t u = 1, v = 0, q = 0, r = 1, jl = jac;
-    int32_t e = eta;
-#pragma unroll
-    for (int i = 0; i < JAC_K; ++i) {
-      const uint32_t m = 0u - (g0 & 1u);                       // g odd
-      const uint32_t sw = m & (uint32_t)(e >> 31);             // ... and eta < 0: swap
-      jl ^= f0 & g0 & sw;
-      uint32_t t = (f0 ^ g0) & sw; f0 ^= t; g0 ^= t;
-      t = (u ^ q) & sw; u ^= t; q ^= t;
-      t = (v ^ r) & sw; v ^= t; r ^= t;
-      e = (e ^ (int32_t)sw) - (int32_t)sw;
-      g0 += f0 & m; q += u & m; r += v & m;
-      g0 >>= 1; u <<= 1; v <<= 1; e -= 1;
-      jl ^= f0 ^ (f0 >> 1);
-    }
+    const uint32_t f0 = f[0] | (f[1] << LW), g0 = g[0] | (g[1] << LW);
+    uint32_t jl = jac;
+    JacTrans t;
+    const int32_t e = jac_steps_var<true>(eta, f0, g0, done ? 0 : JAC_K, t, jl);
+    const uint32_t u = t.u, v = t.v, q = t.q, r = t.r;
     // (f, g) <- (u f + v g, q f + r g) / 2^29: the low limb of both sums is zero by construction
     uint32_t nf[NL], ng[NL];
     uint64_t af = mad(u, f[0], (uint64_t)v * g[0]) >> LW, ag = mad(q, f[0], (uint64_t)r * g[0]) >> LW;
@@ -734,12 +782,14 @@ VRF_HD bool fe_is_square_or_zero(const Fe<L, V>& w, const SqrtTables& T) {
 // 1 / a by the positive divsteps of the Jacobi symbol above with the cofactors kept: f = q, g = the canonical Montgomery
 // image a~, and f = d a~, g = e a~ (mod q) throughout.  The round's 2x2 matrix (entries <= 2^29, rows summing to at most
 // 2^29) is applied to (f, g) -- an exact division by 2^29 -- and to (d, e), where the multiple of q that makes the division
-// exact is (low limb) * (-q^-1 mod 2^29): -(low limb) when q = 1 (mod 2^29).  f = 1 ends a lane with d = a~^-1 < (rounds + 1) q.  About 27 rounds of
-// ~650 instructions (~18 k) against 255 squarings + 30 products (~60 k) for a^(q-2): one inversion per 8 proofs in the big
-// batches, but up to three per proof when a batch is small enough for one proof per lane.  0 -> 0, as the power gives.
+// exact is (low limb) * (-q^-1 mod 2^29): -(low limb) when q = 1 (mod 2^29).  f = 1 ends a lane with d = a~^-1 < (rounds + 1) q:
+// each round maps d, e < k q to u d + v e + md q < (2^29 k + 2^29) q / 2^29 = (k + 1) q.  About 27 rounds; the steps of a
+// round run several at a time (jac_steps_var), ~13 iterations for a wave against 29 single steps, with the matrix product
+// unchanged: ~11 % fewer VALU instructions in the verify finish kernel, whose main cost this is.  Against 255 squarings +
+// 30 products (~60 k) for a^(q-2).  0 -> 0, as the power gives.
 // CT = true (the prover's inversions: the Z coordinates of sk*H, k*H, k*G depend on secrets): every lane runs all
-// JAC_MAX_ROUNDS rounds, so the time no longer follows the operand.  Verification and decoding invert public
-// data and keep the early exit (~27 rounds instead of 40).
+// JAC_MAX_ROUNDS rounds of 29 single steps (jac_steps_ct), so the time no longer follows the operand.
+// Verification and decoding invert public data and keep the early exit (~27 rounds instead of 40) and the variable steps.
 template <bool CT = false, int L, int V>
 VRF_HD FeN fe_inv(const Fe<L, V>& a) {
   const FeN c = fe_canon(a);
@@ -752,20 +802,16 @@ VRF_HD FeN fe_inv(const Fe<L, V>& a) {
 #pragma unroll 1
   for (int round = 0; round < JAC_MAX_ROUNDS; ++round) {
     if (!CT && !vrf_any(!done)) break;
-    uint32_t f0 = f[0] | (f[1] << LW), g0 = g[0] | (g[1] << LW);
-    uint32_t u = 1, v = 0, q = 0, r = 1;
-    int32_t et = eta;
-#pragma unroll
-    for (int i = 0; i < JAC_K; ++i) {
-      const uint32_t m = 0u - (g0 & 1u);                       // g odd
-      const uint32_t sw = m & (uint32_t)(et >> 31);            // ... and eta < 0: swap
-      uint32_t t = (f0 ^ g0) & sw; f0 ^= t; g0 ^= t;
-      t = (u ^ q) & sw; u ^= t; q ^= t;
-      t = (v ^ r) & sw; v ^= t; r ^= t;
-      et = (et ^ (int32_t)sw) - (int32_t)sw;
-      g0 += f0 & m; q += u & m; r += v & m;
-      g0 >>= 1; u <<= 1; v <<= 1; et -= 1;
+    const uint32_t f0 = f[0] | (f[1] << LW), g0 = g[0] | (g[1] << LW);
+    JacTrans t;
+    int32_t et;
+    if constexpr (CT) {
+      et = jac_steps_ct(eta, f0, g0, t);
+    } else {
+      uint32_t no_sign = 0;
+      et = jac_steps_var<false>(eta, f0, g0, done ? 0 : JAC_K, t, no_sign);
     }
+    const uint32_t u = t.u, v = t.v, q = t.q, r = t.r;
     uint32_t nf[NL], ng[NL], nd[NL], ne[NL];
     uint64_t af = mad(u, f[0], (uint64_t)v * g[0]) >> LW, ag = mad(q, f[0], (uint64_t)r * g[0]) >> LW;
     const uint64_t td = mad(u, d[0], (uint64_t)v * e[0]), te = mad(q, d[0], (uint64_t)r * e[0]);

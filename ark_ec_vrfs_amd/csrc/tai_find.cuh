@@ -18,7 +18,7 @@ VRF_NS_BEGIN
 // succeeded records the counter and takes the next item at once, so a wave performs about two attempts per
 // item and the only idle lanes are those of the last few iterations of the whole grid.
 // An attempt has a cheap half (hash the counter, y < q, denominator non-zero) and an expensive one (the Jacobi symbol,
-// four times the hash).  Where the cheap half rejects often -- Baby-JubJub: q = 0.378 * 2^255, five hashes per point --
+// several times the hash even with the multi-step divsteps of fe.cuh).  Where the cheap half rejects often -- Baby-JubJub: q = 0.378 * 2^255, five hashes per point --
 // a wave that ran both halves every trip would run the symbol for the one lane in three that needs it; so a lane that
 // passed the cheap half WAITS (ready), the others keep hashing, and the wave runs the symbol once three quarters of its
 // lanes are ready (or nobody is left to hash).  Suites whose candidates rarely fail the cheap half (JubJub 0.91,
