@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -69,15 +70,20 @@ int32_t fail(int32_t code, const std::string& msg) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t e__ = (expr);                                                               \
-    if (e__ != hipSuccess)                                                                 \
-      return fail(e__ == hipErrorOutOfMemory ? VRFHIP_ERR_OOM : VRFHIP_ERR_HIP,            \
-                  std::string(#expr) + ": " + hipGetErrorString(e__));                     \
+// the one mapping of a HIP error to a return code and a vrfhip_last_error text
+int32_t hip_fail(hipError_t e, const char* what) {
+  return fail(e == hipErrorOutOfMemory ? VRFHIP_ERR_OOM : VRFHIP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+#define HIP_TRY_AS(what, expr)                            \
+  do {                                                    \
+    hipError_t e__ = (expr);                              \
+    if (e__ != hipSuccess) return hip_fail(e__, what);    \
   } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(#expr, expr)
 
 constexpr size_t DEFAULT_CHUNK = size_t(1) << 20;
+const char P256_UNSUPPORTED_MSG[] =
+    "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)";
 const char BSW_UNSUPPORTED_MSG[] =
     "not available for the bandersnatch_sw suite (secret keys, hash-to-curve, output hash, point validation, the IETF scheme incl. "
     "verification from alpha, the x || y forms, key sets, the Pedersen scheme per proof and batched, MSM, and the pairing / G1 "
@@ -136,6 +142,8 @@ struct vrfhip_ctx {
   size_t hash_bytes() const { return sw ? 32 : 64; }      // `Output::hash`: the suite hasher's output
   size_t prove_point_bytes() const { return (flags & VRFHIP_FLAG_PROVE_POINTS_AFFINE) ? 64 : pt_bytes(); }
   bool coords_mont256() const { return (flags & VRFHIP_FLAG_COORDS_MONT256) != 0; }
+  // the kernels' affine_in / out_affine: 0 = encoded points, 1 = x || y canonical, 2 = x || y Montgomery-256
+  int affine_in(bool affine) const { return affine ? (coords_mont256() ? 2 : 1) : 0; }
   // optional per-stage timing (hipEvents on the launch stream), see vrfhip_ctx_profile
   bool prof = false;
   std::vector<hipEvent_t> prof_ev;   // 5 per launch group
@@ -237,18 +245,54 @@ int32_t ensure_msm_workspace(vrfhip_ctx* ctx, size_t need) {
   return VRFHIP_SUCCESS;
 }
 
-// bump allocator over the staging buffer
+// owners of partly built objects and of temporary device buffers: an early return releases them
+struct CtxDestroy { void operator()(vrfhip_ctx* c) const { vrfhip_ctx_destroy(c); } };
+struct KeysetDestroy { void operator()(vrfhip_keyset* k) const { vrfhip_keyset_destroy(k); } };
+template <class T>
+struct DevTmp {
+  T* p = nullptr;
+  ~DevTmp() { if (p) (void)hipFree(p); }
+  T** operator&() { return &p; }
+  operator T*() const { return p; }
+};
+
+// bump allocator over the staging buffer; with a null base it only measures (off = the bytes a layout needs)
 struct Stage {
   uint8_t* base;
   size_t off = 0;
   explicit Stage(void* b) : base(static_cast<uint8_t*>(b)) {}
   static size_t pad(size_t n) { return (n + 255) & ~size_t(255); }
   uint8_t* take(size_t n) {
-    uint8_t* p = base + off;
+    uint8_t* p = base ? base + off : nullptr;
     off += pad(n);
     return p;
   }
 };
+// A host-pointer entry point writes its staging layout once, as carve(Stage&).  Run on a measuring Stage it gives the size
+// the buffer must have; run again on the buffer it hands out the regions: the two cannot disagree.
+template <class F>
+int32_t stage_layout(vrfhip_ctx* ctx, F carve) {
+  Stage measure(nullptr);
+  carve(measure);
+  int32_t rc = ensure_stage(ctx, measure.off);
+  if (rc) return rc;
+  Stage sg(ctx->d_stage);
+  carve(sg);
+  return VRFHIP_SUCCESS;
+}
+
+// f(base, m) for the chunks [base, base + m) of a batch of n items, at most cap each; the first failure ends it
+template <class F>
+int32_t for_chunks(size_t n, size_t cap, F f) {
+  for (size_t base = 0; base < n; base += cap) {
+    int32_t rc = f(base, std::min(cap, n - base));
+    if (rc) return rc;
+  }
+  return VRFHIP_SUCCESS;
+}
+// item i of an array of w-byte items that may be absent
+template <class T>
+T* at(T* p, size_t i, size_t w) { return p ? p + i * w : nullptr; }
 
 // five fresh events for one launch group when profiling is on, else nullptr
 hipEvent_t* prof_events(vrfhip_ctx* ctx) {
@@ -318,19 +362,44 @@ int32_t pipe_send(vrfhip_ctx* ctx, const PipeArr* arrs, const bool* pinned, int 
   return VRFHIP_SUCCESS;
 }
 
-BytesView make_view(const uint8_t* blob, const uint32_t* off, uint32_t len, bool shared) {
-  BytesView v;
-  v.blob = blob;
-  v.off = off;
-  v.len = len;
-  v.stride = shared ? 0u : len;
-  return v;
-}
-
-// size in bytes of a host-side variable-length blob
-size_t blob_bytes(size_t n, const uint32_t* off, uint32_t len, bool shared) {
-  if (off) return off[n];
-  return shared ? len : n * (size_t)len;
+// The byte strings of a batch (messages, additional data), in host or device memory: n + 1 offsets into p, or -- off ==
+// nullptr -- len bytes per item, one string for all items (shared) or one after the other.
+struct Blob {
+  const uint8_t* p;
+  const uint32_t* off;
+  uint32_t len;
+  bool shared;
+  bool missing() const { return (len || off) && !p; }
+  // bytes of a host-side blob of n items (an absent one has none)
+  size_t bytes(size_t n) const { return off ? off[n] : !p ? 0 : shared ? len : n * (size_t)len; }
+  // what the kernels of the chunk that starts at item `base` read (bytes_lite_get: len and stride count only without off)
+  BytesView view(size_t base) const {
+    BytesView v;
+    v.blob = (off || shared || !p) ? p : p + base * (size_t)len;
+    v.off = off ? off + base : nullptr;
+    v.len = len;
+    v.stride = shared ? 0u : len;
+    return v;
+  }
+};
+// a host blob on its way through the staging buffer: room for its bytes (+ 1: never an empty region) and its offsets
+struct StagedBlob {
+  Blob h;
+  size_t n, nb;
+  uint8_t* d = nullptr;
+  uint32_t* d_off = nullptr;
+  StagedBlob(const Blob& host, size_t items) : h(host), n(items), nb(host.bytes(items)) {}
+  void take(Stage& sg) {
+    d = sg.take(nb + 1);
+    d_off = reinterpret_cast<uint32_t*>(sg.take((n + 1) * 4));
+  }
+};
+// uploads the blob and its offsets, if it has any, on the context's stream; *out = the device-side Blob
+int32_t stage_blob(vrfhip_ctx* ctx, const StagedBlob& b, Blob* out) {
+  if (b.nb) HIP_TRY(hipMemcpyAsync(b.d, b.h.p, b.nb, hipMemcpyHostToDevice, ctx->stream));
+  if (b.h.off) HIP_TRY(hipMemcpyAsync(b.d_off, b.h.off, (b.n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+  *out = Blob{b.d, b.h.off ? b.d_off : nullptr, b.h.len, b.h.shared};
+  return VRFHIP_SUCCESS;
 }
 
 }  // namespace
@@ -459,23 +528,14 @@ int32_t vrfhip_ctx_create_desc(const vrfhip_suite_desc* desc, int32_t device, vr
   if (device < 0 || device >= count) return fail(VRFHIP_ERR_BAD_ARG, "device index out of range");
   DeviceGuard guard(device);
   if (!guard.ok) return fail(VRFHIP_ERR_HIP, "hipSetDevice failed");
-  vrfhip_ctx* ctx = new vrfhip_ctx();
+  std::unique_ptr<vrfhip_ctx, CtxDestroy> owner(new vrfhip_ctx());    // destroyed by every return but the last
+  vrfhip_ctx* ctx = owner.get();
   ctx->device = device;
   ctx->suite = suite;
   ctx->field = suite_field((int)suite);
   ctx->bsw = bsw;
   ctx->desc = *desc;
-  auto cleanup = [&](int32_t rc) {
-    vrfhip_ctx_destroy(ctx);
-    return rc;
-  };
-#define HIP_TRY_C(expr)                                                                   \
-  do {                                                                                    \
-    hipError_t e__ = (expr);                                                              \
-    if (e__ != hipSuccess)                                                                \
-      return cleanup(fail(VRFHIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__))); \
-  } while (0)
-  HIP_TRY_C(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+  HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
@@ -489,34 +549,32 @@ int32_t vrfhip_ctx_create_desc(const vrfhip_suite_desc* desc, int32_t device, vr
     hs.challenge_len = desc->challenge_len;
     for (size_t i = 0; i < desc->suite_id_len; ++i) hs.suite_id_w[i >> 3] |= (uint64_t)desc->suite_id[i] << (56 - 8 * (i & 7));
     ctx->T.sq.str = hs;
-    uint8_t* d_gen = nullptr;
-    HIP_TRY_C(hipMalloc(&ctx->d_p256_comb, p256::comb_bytes()));
-    HIP_TRY_C(hipMalloc(&ctx->d_queue, 256));
-    HIP_TRY_C(hipMalloc(&d_gen, 256));
+    DevTmp<uint8_t> d_gen;
+    HIP_TRY(hipMalloc(&ctx->d_p256_comb, p256::comb_bytes()));
+    HIP_TRY(hipMalloc(&ctx->d_queue, 256));
+    HIP_TRY(hipMalloc(&d_gen, 256));
     uint8_t gen_ok = 0;
     hipError_t e0 = hipMemcpyAsync(d_gen, desc->generator, 64, hipMemcpyHostToDevice, ctx->stream);   // ordered with the kernel below
     p256::launch_init_comb(ctx->d_p256_comb, d_gen, d_gen + 128, ctx->stream);
     hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(ctx->stream);
     hipError_t e3 = hipMemcpy(&gen_ok, d_gen + 128, 1, hipMemcpyDeviceToHost);
-    (void)hipFree(d_gen);
-    HIP_TRY_C(e0); HIP_TRY_C(e1); HIP_TRY_C(e2); HIP_TRY_C(e3);
-    if (!gen_ok) return cleanup(fail(VRFHIP_ERR_BAD_ARG, "desc.generator is not a point of the curve"));
+    HIP_TRY(e0); HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3);
+    if (!gen_ok) return fail(VRFHIP_ERR_BAD_ARG, "desc.generator is not a point of the curve");
     bool have_b = false;
     for (size_t i = 0; i < 64; ++i) have_b = have_b || desc->blinding_base[i] != 0;
     if (have_b) {                               // `PedersenSuite::BLINDING_BASE`; all-zero = a suite without the Pedersen scheme
-      uint8_t* d_b = nullptr;
-      HIP_TRY_C(hipMalloc(&ctx->d_p256_comb_b, p256::comb_bytes()));
-      HIP_TRY_C(hipMalloc(&d_b, 256));
+      DevTmp<uint8_t> d_b;
+      HIP_TRY(hipMalloc(&ctx->d_p256_comb_b, p256::comb_bytes()));
+      HIP_TRY(hipMalloc(&d_b, 256));
       uint8_t b_ok = 0;
       hipError_t f0 = hipMemcpyAsync(d_b, desc->blinding_base, 64, hipMemcpyHostToDevice, ctx->stream);
       p256::launch_init_comb(ctx->d_p256_comb_b, d_b, d_b + 128, ctx->stream);
       hipError_t f1 = hipGetLastError(), f2 = hipStreamSynchronize(ctx->stream);
       hipError_t f3 = hipMemcpy(&b_ok, d_b + 128, 1, hipMemcpyDeviceToHost);
-      (void)hipFree(d_b);
-      HIP_TRY_C(f0); HIP_TRY_C(f1); HIP_TRY_C(f2); HIP_TRY_C(f3);
-      if (!b_ok) return cleanup(fail(VRFHIP_ERR_BAD_ARG, "desc.blinding_base is not a point of the curve"));
+      HIP_TRY(f0); HIP_TRY(f1); HIP_TRY(f2); HIP_TRY(f3);
+      if (!b_ok) return fail(VRFHIP_ERR_BAD_ARG, "desc.blinding_base is not a point of the curve");
     }
-    *out = ctx;
+    *out = owner.release();
     return VRFHIP_SUCCESS;
   }
   size_t sqrt_p_bytes = 0, lut_bytes = 0;
@@ -529,18 +587,18 @@ int32_t vrfhip_ctx_create_desc(const vrfhip_suite_desc* desc, int32_t device, vr
   }
   const size_t comb_bytes = GCOMB_WORDS * sizeof(uint32_t);            // 56.6 MB per generator (16-bit signed windows)
   const size_t prefix_bytes = (size_t)2 * GC_ROWS * GC_SEGS * GC_SEG * NL * sizeof(uint32_t);
-  uint32_t* d_prefix = nullptr;
-  uint8_t* d_init = nullptr;          // 128 B points | 36 words Montgomery | 2 B flags
-  HIP_TRY_C(hipMalloc(&ctx->d_sqrt_p, sqrt_p_bytes));
-  HIP_TRY_C(hipMalloc(&ctx->d_sqrt_lut, lut_bytes));
-  HIP_TRY_C(hipMalloc(&ctx->d_g_win, 2 * WIN_TABLE_WORDS * sizeof(uint32_t)));
-  HIP_TRY_C(hipMalloc(&ctx->d_g_comb, comb_bytes));
-  HIP_TRY_C(hipMalloc(&ctx->d_b_comb, comb_bytes));
-  HIP_TRY_C(hipMalloc(&ctx->d_queue, 256));
-  HIP_TRY_C(hipMalloc(&ctx->d_pair_prep, pairing_prep_bytes()));
-  HIP_TRY_C(hipMemset(ctx->d_pair_prep, 0, pairing_prep_bytes()));
-  HIP_TRY_C(hipMemcpyAsync(ctx->d_sqrt_p, h_sqrt_p, sqrt_p_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY_C(hipMemcpyAsync(ctx->d_sqrt_lut, h_sqrt_lut, lut_bytes, hipMemcpyHostToDevice, ctx->stream));
+  DevTmp<uint32_t> d_prefix;
+  DevTmp<uint8_t> d_init;             // 128 B points | 36 words Montgomery | 2 B flags
+  HIP_TRY(hipMalloc(&ctx->d_sqrt_p, sqrt_p_bytes));
+  HIP_TRY(hipMalloc(&ctx->d_sqrt_lut, lut_bytes));
+  HIP_TRY(hipMalloc(&ctx->d_g_win, 2 * WIN_TABLE_WORDS * sizeof(uint32_t)));
+  HIP_TRY(hipMalloc(&ctx->d_g_comb, comb_bytes));
+  HIP_TRY(hipMalloc(&ctx->d_b_comb, comb_bytes));
+  HIP_TRY(hipMalloc(&ctx->d_queue, 256));
+  HIP_TRY(hipMalloc(&ctx->d_pair_prep, pairing_prep_bytes()));
+  HIP_TRY(hipMemset(ctx->d_pair_prep, 0, pairing_prep_bytes()));
+  HIP_TRY(hipMemcpyAsync(ctx->d_sqrt_p, h_sqrt_p, sqrt_p_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ctx->d_sqrt_lut, h_sqrt_lut, lut_bytes, hipMemcpyHostToDevice, ctx->stream));
   // the suite's byte strings, packed big-endian into the 64-bit words SHA-512 absorbs; they travel in the kernel
   // arguments (SuiteStr, fe.cuh)
   SuiteStr hs{};
@@ -567,16 +625,15 @@ int32_t vrfhip_ctx_create_desc(const vrfhip_suite_desc* desc, int32_t device, vr
     ctx->have_blinding = have_b;
     if (!have_b) std::memcpy(gb + 64, desc->generator, 64);   // the table kernel wants a valid point; the scheme stays off
   }
-  HIP_TRY_C(hipMalloc(&d_init, 512));
-  HIP_TRY_C(hipMalloc(&d_prefix, prefix_bytes));
-  auto free_tmp = [&]() { (void)hipFree(d_prefix); (void)hipFree(d_init); };
+  HIP_TRY(hipMalloc(&d_init, 512));
+  HIP_TRY(hipMalloc(&d_prefix, prefix_bytes));
   ctx->T.sq.P = ctx->d_sqrt_p;
   ctx->T.sq.lut = ctx->d_sqrt_lut;
   ctx->T.sq.str = hs;
   {
     // on the context's stream: ordered in front of the table kernels by construction (gb outlives the synchronisation below)
     hipError_t e1 = hipMemcpyAsync(d_init, gb, sizeof gb, hipMemcpyHostToDevice, ctx->stream);
-    if (e1 != hipSuccess) { free_tmp(); HIP_TRY_C(e1); }
+    HIP_TRY(e1);
   }
   uint32_t* d_mont = reinterpret_cast<uint32_t*>(d_init + 128);
   uint8_t* d_flags = d_init + 128 + 4 * NL * sizeof(uint32_t);
@@ -590,14 +647,9 @@ int32_t vrfhip_ctx_create_desc(const vrfhip_suite_desc* desc, int32_t device, vr
     // on the context's stream, in front of the table kernels: a device-to-device hipMemcpy on the null stream need not have
     // finished when it returns, and the (non-blocking) stream would not wait for it
     hipError_t e4 = hipMemcpyAsync(d_init, d_init + 288, 128, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
-      free_tmp();
-      HIP_TRY_C(e1); HIP_TRY_C(e2); HIP_TRY_C(e3); HIP_TRY_C(e4);
-    }
-    if (map_st[0] || map_st[1]) {
-      free_tmp();
-      return cleanup(fail(VRFHIP_ERR_BAD_ARG, map_st[0] ? "desc.generator has no twisted-Edwards image" : "desc.blinding_base has no twisted-Edwards image"));
-    }
+    HIP_TRY(e1); HIP_TRY(e2); HIP_TRY(e3); HIP_TRY(e4);
+    if (map_st[0] || map_st[1])
+      return fail(VRFHIP_ERR_BAD_ARG, map_st[0] ? "desc.generator has no twisted-Edwards image" : "desc.blinding_base has no twisted-Edwards image");
   }
   FIELD_CALL(ctx, launch_init_tables((int)suite, ctx->d_g_win, ctx->d_g_comb, ctx->d_b_comb, d_prefix, d_init, d_mont, d_flags, ctx->T.sq,
                      ctx->stream));
@@ -605,18 +657,16 @@ int32_t vrfhip_ctx_create_desc(const vrfhip_suite_desc* desc, int32_t device, vr
   {
     hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(ctx->stream);
     hipError_t e3 = hipMemcpy(base_ok, d_flags, 2, hipMemcpyDeviceToHost);
-    free_tmp();
-    HIP_TRY_C(e1);
-    HIP_TRY_C(e2);
-    HIP_TRY_C(e3);
+    HIP_TRY(e1);
+    HIP_TRY(e2);
+    HIP_TRY(e3);
   }
-#undef HIP_TRY_C
-  if (!base_ok[0]) return cleanup(fail(VRFHIP_ERR_BAD_ARG, "desc.generator is not a non-identity point of the prime-order subgroup"));
-  if (!base_ok[1]) return cleanup(fail(VRFHIP_ERR_BAD_ARG, "desc.blinding_base is not a non-identity point of the prime-order subgroup"));
+  if (!base_ok[0]) return fail(VRFHIP_ERR_BAD_ARG, "desc.generator is not a non-identity point of the prime-order subgroup");
+  if (!base_ok[1]) return fail(VRFHIP_ERR_BAD_ARG, "desc.blinding_base is not a non-identity point of the prime-order subgroup");
   ctx->T.g_win = ctx->d_g_win;
   ctx->T.g_comb = ctx->d_g_comb;
   ctx->T.b_comb = ctx->d_b_comb;
-  *out = ctx;
+  *out = owner.release();
   return VRFHIP_SUCCESS;
 }
 
@@ -747,102 +797,83 @@ int32_t vrfhip_ctx_profile_read(vrfhip_ctx* ctx, double stage_ms[4], uint64_t* l
 
 namespace {
 int32_t verify_dev_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* d_pk, const uint8_t* d_input,
-                        const uint8_t* d_output, const uint8_t* d_c, const uint8_t* d_s, const uint8_t* d_ad,
-                        const uint32_t* d_ad_off, uint32_t ad_len, uint8_t* d_status, void* stream,
-                        const vrfhip_keyset* ks = nullptr, const uint32_t* d_key_index = nullptr) {
+                        const uint8_t* d_output, const uint8_t* d_c, const uint8_t* d_s, const Blob& ad, uint8_t* d_status,
+                        void* stream, const vrfhip_keyset* ks = nullptr, const uint32_t* d_key_index = nullptr) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (ks && (ks->ctx != ctx || !d_key_index)) return fail(VRFHIP_ERR_BAD_ARG, "key set of another context, or NULL key index");
   if (n == 0) return VRFHIP_SUCCESS;
   if (ks) d_pk = ks->d_enc;
   if (!d_pk || !d_input || !d_output || !d_c || !d_s || !d_status)
     return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
-  if ((ad_len || d_ad_off) && !d_ad) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
+  if (ad.missing()) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
   int32_t rc = ensure_workspace(ctx, n);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (ctx->sw) {
-    for (size_t base = 0; base < n; base += ctx->ws_cap) {
-      const size_t m = std::min(ctx->ws_cap, n - base);
-      p256::VerifyArgs a{};
+  const size_t pw = affine ? 64 : ctx->pt_bytes();
+  rc = for_chunks(n, ctx->ws_cap, [&](size_t base, size_t m) -> int32_t {
+    auto common = [&](auto& a) {
       a.n = m;
-      const size_t pw = affine ? 64 : 33;
       a.pk = d_pk + base * pw; a.h = d_input + base * pw; a.gamma = d_output + base * pw;
-      a.affine_in = affine ? (ctx->coords_mont256() ? 2 : 1) : 0;
+      a.affine_in = ctx->affine_in(affine);
       a.c = d_c + base * 32; a.s = d_s + base * 32;
-      a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
+      a.ad = ad.view(base);
       a.status = d_status + base;
+      if (ks) { a.key_index = d_key_index + base; a.n_keys = ks->n_keys; a.key_valid = ks->d_valid; a.key_combs = ks->d_combs; }
+    };
+    if (ctx->sw) {
+      p256::VerifyArgs a{};
+      common(a);
       a.ws = ctx->p256_ws;
       a.comb = ctx->d_p256_comb;
       a.str = ctx->T.sq.str;
-      if (ks) {
-        a.pk = nullptr;
-        a.key_index = d_key_index + base; a.n_keys = ks->n_keys; a.key_enc = ks->d_enc; a.key_aff = ks->d_aff;
-        a.key_valid = ks->d_valid; a.key_combs = ks->d_combs; a.key_rows = ks->rows;
-      }
+      if (ks) { a.pk = nullptr; a.key_enc = ks->d_enc; a.key_aff = ks->d_aff; a.key_rows = ks->rows; }
       p256::launch_verify(a, st, prof_events(ctx));
+      return VRFHIP_SUCCESS;
     }
-    HIP_TRY(hipGetLastError());
-    return VRFHIP_SUCCESS;
-  }
-  const size_t pw = affine ? 64 : ctx->pt_bytes();
-  for (size_t base = 0; base < n; base += ctx->ws_cap) {
-    size_t m = std::min(ctx->ws_cap, n - base);
-    VerifyArgs a;
+    VerifyArgs a{};
+    common(a);
     a.suite = (int)ctx->suite;
     a.k_lane = lanes_k(m, VERIFY_K_POLICY);
-    a.n = m;
-    a.pk = ks ? d_pk : d_pk + base * pw; a.h = d_input + base * pw; a.gamma = d_output + base * pw;
-    a.affine_in = affine ? (ctx->coords_mont256() ? 2 : 1) : 0;
-    a.h_in_tabs = 0;
+    if (ks) a.pk = ks->d_enc;                 // the key set's encodings, not a per-proof array
     a.check_mask = ctx->check_mask();
-    a.key_index = ks ? d_key_index + base : nullptr;
-    a.key_combs = ks ? ks->d_combs : nullptr;
-    a.key_valid = ks ? ks->d_valid : nullptr;
-    a.n_keys = ks ? ks->n_keys : 0;
-    a.c = d_c + base * 32; a.s = d_s + base * 32;
-    a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
-    a.status = d_status + base;
     a.ws = ctx->ws;
     a.T = ctx->T;
     if (ctx->bsw) launch_bsw_ietf_verify(a, st, prof_events(ctx));
     else FIELD_CALL(ctx, launch_ietf_verify(a, st, prof_events(ctx)));
-  }
+    return VRFHIP_SUCCESS;
+  });
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return VRFHIP_SUCCESS;
 }
 
 int32_t verify_host_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* pk, const uint8_t* input,
-                         const uint8_t* output, const uint8_t* c, const uint8_t* s, const uint8_t* ad,
-                         const uint32_t* ad_off, uint32_t ad_len, uint8_t* status) {
+                         const uint8_t* output, const uint8_t* c, const uint8_t* s, const Blob& ad, uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
   if (!pk || !input || !output || !c || !s || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
-  if ((ad_len || ad_off) && !ad) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
-  size_t adb = blob_bytes(n, ad_off, ad_len, true);
+  if (ad.missing()) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
+  StagedBlob s_ad(ad, n);
   const size_t pw = affine ? 64 : ctx->pt_bytes();
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  size_t need = 3 * Stage::pad(n * pw) + 2 * Stage::pad(n * 32) + Stage::pad(adb + 1) +
-                Stage::pad((n + 1) * 4) + Stage::pad(n);
-  int32_t rc = ensure_stage(ctx, need);
+  uint8_t *d_pk, *d_h, *d_g, *d_c, *d_s, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
+    d_pk = sg.take(n * pw); d_h = sg.take(n * pw); d_g = sg.take(n * pw);
+    d_c = sg.take(n * 32); d_s = sg.take(n * 32);
+    s_ad.take(sg);
+    d_st = sg.take(n);
+  });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t* d_pk = sg.take(n * pw);
-  uint8_t* d_h = sg.take(n * pw);
-  uint8_t* d_g = sg.take(n * pw);
-  uint8_t* d_c = sg.take(n * 32);
-  uint8_t* d_s = sg.take(n * 32);
-  uint8_t* d_ad = sg.take(adb + 1);
-  uint32_t* d_off = reinterpret_cast<uint32_t*>(sg.take((n + 1) * 4));
-  uint8_t* d_st = sg.take(n);
-  if (adb) HIP_TRY(hipMemcpyAsync(d_ad, ad, adb, hipMemcpyHostToDevice, ctx->stream));
-  if (ad_off) HIP_TRY(hipMemcpyAsync(d_off, ad_off, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+  Blob d_ad;
+  rc = stage_blob(ctx, s_ad, &d_ad);
+  if (rc) return rc;
   const PipeArr arrs[5] = {{pk, d_pk, pw}, {input, d_h, pw}, {output, d_g, pw}, {c, d_c, 32}, {s, d_s, 32}};
   if (n <= PIPE_CHUNK) {                         // one chunk: nothing to overlap with
     for (const PipeArr& a : arrs) HIP_TRY(hipMemcpyAsync(a.d, a.h, n * a.w, hipMemcpyHostToDevice, ctx->stream));
-    rc = verify_dev_impl(ctx, n, affine, d_pk, d_h, d_g, d_c, d_s, d_ad, ad_off ? d_off : nullptr, ad_len, d_st, ctx->stream);
+    rc = verify_dev_impl(ctx, n, affine, d_pk, d_h, d_g, d_c, d_s, d_ad, d_st, ctx->stream);
     if (rc) return rc;
   } else {
     bool pinned[5];
@@ -860,8 +891,10 @@ int32_t verify_host_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* 
       m = std::min(base == 0 ? first_chunk : chunk, n - base);
       rc = pipe_send(ctx, arrs, pinned, 5, base, m, slot);
       if (rc) return rc;
+      Blob ad_m = d_ad;                          // this chunk's slice: per-item offsets move on, a shared string stays
+      if (ad_m.off) ad_m.off += base;
       rc = verify_dev_impl(ctx, m, affine, d_pk + base * pw, d_h + base * pw, d_g + base * pw, d_c + base * 32, d_s + base * 32,
-                           d_ad, ad_off ? d_off + base : nullptr, ad_len, d_st + base, ctx->stream);
+                           ad_m, d_st + base, ctx->stream);
       if (rc) return rc;
     }
   }
@@ -878,102 +911,77 @@ int32_t vrfhip_ietf_verify_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d
                                      const uint8_t* d_c, const uint8_t* d_s, const uint8_t* d_ad,
                                      const uint32_t* d_ad_off, uint32_t ad_len, uint8_t* d_status,
                                      void* stream) {
-  return verify_dev_impl(ctx, n, false, d_pk, d_input, d_output, d_c, d_s, d_ad, d_ad_off, ad_len, d_status,
+  return verify_dev_impl(ctx, n, false, d_pk, d_input, d_output, d_c, d_s, Blob{d_ad, d_ad_off, ad_len, true}, d_status,
                          stream);
 }
 // `Input::new(alpha)` + `ietf::Verifier::verify` in one launch group: H never leaves the device and is never compressed,
 // decompressed or subgroup-tested (k_verify.hip k_verify_input_from_alpha).  Per chunk of the workspace: hash-to-curve writes
-// enc(H) into the (otherwise idle) aux region and H's tables into slot 1, the decode stage handles pk and Gamma.
+// enc(H) into an otherwise idle region, the decode stage handles pk and Gamma.
 int32_t vrfhip_ietf_verify_batch_alpha_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_pk, const uint8_t* d_msg,
                                            const uint32_t* d_msg_off, uint32_t msg_len, const uint8_t* d_output,
                                            const uint8_t* d_c, const uint8_t* d_s, const uint8_t* d_ad,
                                            const uint32_t* d_ad_off, uint32_t ad_len, uint8_t* d_status, void* stream) {
+  const Blob msg{d_msg, d_msg_off, msg_len, false}, ad{d_ad, d_ad_off, ad_len, true};
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
-  if (!d_pk || !d_output || !d_c || !d_s || !d_status || (!d_msg && (msg_len || d_msg_off)))
-    return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
-  if ((ad_len || d_ad_off) && !d_ad) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
+  if (!d_pk || !d_output || !d_c || !d_s || !d_status || msg.missing()) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  if (ad.missing()) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
   int32_t rc = ensure_workspace(ctx, n);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (ctx->sw) {
-    // secp256r1: the two stages as they are (cofactor 1: there is no subgroup test to skip), H's Sec1 string parked in the
-    // projective-results region, which nothing writes before the decode stage has read it
-    for (size_t base = 0; base < n; base += ctx->ws_cap) {
-      const size_t m = std::min(ctx->ws_cap, n - base);
-      uint8_t* d_henc = reinterpret_cast<uint8_t*>(ctx->p256_ws.pts);
-      BytesView mv = d_msg_off ? make_view(d_msg, d_msg_off + base, msg_len, false)
-                               : make_view(d_msg ? d_msg + base * (size_t)msg_len : d_msg, nullptr, msg_len, false);
+  // Where enc(H) waits between the two stages.  secp256r1: the projective-results region, which nothing writes before the
+  // decode stage has read it (cofactor 1: there is no subgroup test to skip).  bandersnatch_sw: the (otherwise idle) MSM
+  // workspace -- every region of the verify workspace is written by the decode stage.  Edwards: the aux region, [m][32]
+  // (AUX_WORDS * 4 >= 32 bytes per item), with H's tables in slot 1.
+  uint8_t* d_henc;
+  if (ctx->sw) d_henc = reinterpret_cast<uint8_t*>(ctx->p256_ws.pts);
+  else if (ctx->bsw) {
+    rc = ensure_msm_workspace(ctx, std::min(ctx->ws_cap, n) * 33 + 256);
+    if (rc) return rc;
+    d_henc = static_cast<uint8_t*>(ctx->d_msm_ws);
+  } else d_henc = reinterpret_cast<uint8_t*>(ctx->ws.aux);
+  const size_t pw = ctx->pt_bytes();
+  rc = for_chunks(n, ctx->ws_cap, [&](size_t base, size_t m) -> int32_t {
+    const BytesView mv = msg.view(base);
+    auto common = [&](auto& a) {
+      a.n = m;
+      a.pk = d_pk + base * pw; a.h = d_henc; a.gamma = d_output + base * pw;
+      a.c = d_c + base * 32; a.s = d_s + base * 32;
+      a.ad = ad.view(base);
+      a.status = d_status + base;
+    };
+    if (ctx->sw) {
       p256::launch_hash_to_curve(m, mv, d_henc, ctx->T.sq.str, st, ctx->p256_ws.flags, ctx->d_queue);
       p256::VerifyArgs a{};
-      a.n = m;
-      a.pk = d_pk + base * 33; a.h = d_henc; a.gamma = d_output + base * 33;
-      a.affine_in = 0;
-      a.c = d_c + base * 32; a.s = d_s + base * 32;
-      a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
-      a.status = d_status + base;
+      common(a);
       a.ws = ctx->p256_ws;
       a.comb = ctx->d_p256_comb;
       a.str = ctx->T.sq.str;
       p256::launch_verify(a, st, prof_events(ctx));
+      return VRFHIP_SUCCESS;
     }
-    HIP_TRY(hipGetLastError());
-    return VRFHIP_SUCCESS;
-  }
-  if (ctx->bsw) {
-    // the two stages as they are: H's 33-byte strings parked in the (otherwise idle) MSM workspace -- every region of the
-    // verify workspace is written by the decode stage; H is a cofactor multiple by construction, so its subgroup test is skipped
-    {
-      const int32_t rc2 = ensure_msm_workspace(ctx, std::min(ctx->ws_cap, n) * 33 + 256);
-      if (rc2) return rc2;
-    }
-    for (size_t base = 0; base < n; base += ctx->ws_cap) {
-      const size_t m = std::min(ctx->ws_cap, n - base);
-      uint8_t* d_henc = static_cast<uint8_t*>(ctx->d_msm_ws);
-      BytesView mv = d_msg_off ? make_view(d_msg, d_msg_off + base, msg_len, false)
-                               : make_view(d_msg ? d_msg + base * (size_t)msg_len : d_msg, nullptr, msg_len, false);
-      launch_bsw_hash_to_curve(m, mv, d_henc, ctx->T, st, ctx->ws.flags, ctx->d_queue);
-      VerifyArgs a{};
-      a.suite = (int)ctx->suite;
-      a.k_lane = 1;
-      a.n = m;
-      a.pk = d_pk + base * 33; a.h = d_henc; a.gamma = d_output + base * 33;
-      a.check_mask = ctx->check_mask() & ~2u;
-      a.c = d_c + base * 32; a.s = d_s + base * 32;
-      a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
-      a.status = d_status + base;
-      a.ws = ctx->ws;
-      a.T = ctx->T;
-      launch_bsw_ietf_verify(a, st, prof_events(ctx));
-    }
-    HIP_TRY(hipGetLastError());
-    return VRFHIP_SUCCESS;
-  }
-  for (size_t base = 0; base < n; base += ctx->ws_cap) {
-    const size_t m = std::min(ctx->ws_cap, n - base);
-    uint8_t* d_henc = reinterpret_cast<uint8_t*>(ctx->ws.aux);              // [m][32]: AUX_WORDS * 4 >= 32 bytes per item
-    BytesView mv = d_msg_off ? make_view(d_msg, d_msg_off + base, msg_len, false)
-                             : make_view(d_msg ? d_msg + base * (size_t)msg_len : d_msg, nullptr, msg_len, false);
-    FIELD_CALL(ctx, launch_verify_input_from_alpha((int)ctx->suite, m, mv, d_henc, ctx->ws.tabs, ctx->T, st, ctx->ws.flags,
-                                                   ctx->d_queue));
-    VerifyArgs a;
+    VerifyArgs a{};
+    common(a);
     a.suite = (int)ctx->suite;
-    a.k_lane = lanes_k(m, VERIFY_K_POLICY);
-    a.n = m;
-    a.pk = d_pk + base * 32; a.h = d_henc; a.gamma = d_output + base * 32;
-    a.affine_in = 0;
-    a.h_in_tabs = 1;
     a.check_mask = ctx->check_mask() & ~2u;             // CHK_INPUT: H is a cofactor multiple by construction
-    a.key_index = nullptr; a.key_combs = nullptr; a.key_valid = nullptr; a.n_keys = 0;
-    a.c = d_c + base * 32; a.s = d_s + base * 32;
-    a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
-    a.status = d_status + base;
     a.ws = ctx->ws;
     a.T = ctx->T;
-    FIELD_CALL(ctx, launch_ietf_verify(a, st, prof_events(ctx)));
-  }
+    if (ctx->bsw) {                                     // the two stages as they are
+      launch_bsw_hash_to_curve(m, mv, d_henc, ctx->T, st, ctx->ws.flags, ctx->d_queue);
+      a.k_lane = 1;
+      launch_bsw_ietf_verify(a, st, prof_events(ctx));
+    } else {
+      FIELD_CALL(ctx, launch_verify_input_from_alpha((int)ctx->suite, m, mv, d_henc, ctx->ws.tabs, ctx->T, st, ctx->ws.flags,
+                                                     ctx->d_queue));
+      a.k_lane = lanes_k(m, VERIFY_K_POLICY);
+      a.h_in_tabs = 1;
+      FIELD_CALL(ctx, launch_ietf_verify(a, st, prof_events(ctx)));
+    }
+    return VRFHIP_SUCCESS;
+  });
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return VRFHIP_SUCCESS;
 }
@@ -982,33 +990,31 @@ int32_t vrfhip_ietf_verify_batch_alpha(vrfhip_ctx* ctx, size_t n, const uint8_t*
                                        const uint32_t* msg_off, uint32_t msg_len, const uint8_t* output, const uint8_t* c,
                                        const uint8_t* s, const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
                                        uint8_t* status) {
+  const Blob h_msg{msg, msg_off, msg_len, false}, h_ad{ad, ad_off, ad_len, true};
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
-  if (!pk || !output || !c || !s || !status || (!msg && (msg_len || msg_off))) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
-  if ((ad_len || ad_off) && !ad) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
-  const size_t msgb = blob_bytes(n, msg_off, msg_len, false), adb = blob_bytes(n, ad_off, ad_len, true);
+  if (!pk || !output || !c || !s || !status || h_msg.missing()) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  if (h_ad.missing()) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
+  StagedBlob s_msg(h_msg, n), s_ad(h_ad, n);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
   const size_t pw = ctx->pt_bytes();
-  int32_t rc = ensure_stage(ctx, 2 * Stage::pad(n * pw) + 2 * Stage::pad(n * 32) + Stage::pad(msgb + 1) + Stage::pad(adb + 1) +
-                                     2 * Stage::pad((n + 1) * 4) + Stage::pad(n));
+  uint8_t *d_pk, *d_g, *d_c, *d_s, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
+    d_pk = sg.take(n * pw); d_g = sg.take(n * pw); d_c = sg.take(n * 32); d_s = sg.take(n * 32);
+    s_msg.take(sg);
+    s_ad.take(sg);
+    d_st = sg.take(n);
+  });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t *d_pk = sg.take(n * pw), *d_g = sg.take(n * pw), *d_c = sg.take(n * 32), *d_s = sg.take(n * 32);
-  uint8_t *d_msg = sg.take(msgb + 1), *d_ad = sg.take(adb + 1);
-  uint32_t* d_moff = reinterpret_cast<uint32_t*>(sg.take((n + 1) * 4));
-  uint32_t* d_aoff = reinterpret_cast<uint32_t*>(sg.take((n + 1) * 4));
-  uint8_t* d_st = sg.take(n);
   HIP_TRY(hipMemcpyAsync(d_pk, pk, n * pw, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(d_g, output, n * pw, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(d_c, c, n * 32, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(d_s, s, n * 32, hipMemcpyHostToDevice, ctx->stream));
-  if (msgb) HIP_TRY(hipMemcpyAsync(d_msg, msg, msgb, hipMemcpyHostToDevice, ctx->stream));
-  if (adb) HIP_TRY(hipMemcpyAsync(d_ad, ad, adb, hipMemcpyHostToDevice, ctx->stream));
-  if (msg_off) HIP_TRY(hipMemcpyAsync(d_moff, msg_off, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (ad_off) HIP_TRY(hipMemcpyAsync(d_aoff, ad_off, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  rc = vrfhip_ietf_verify_batch_alpha_dev(ctx, n, d_pk, d_msg, msg_off ? d_moff : nullptr, msg_len, d_g, d_c, d_s, d_ad,
-                                          ad_off ? d_aoff : nullptr, ad_len, d_st, ctx->stream);
+  Blob d_msg, d_ad;
+  if ((rc = stage_blob(ctx, s_msg, &d_msg)) || (rc = stage_blob(ctx, s_ad, &d_ad))) return rc;
+  rc = vrfhip_ietf_verify_batch_alpha_dev(ctx, n, d_pk, d_msg.p, d_msg.off, msg_len, d_g, d_c, d_s, d_ad.p, d_ad.off, ad_len,
+                                          d_st, ctx->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1020,20 +1026,20 @@ int32_t vrfhip_ietf_verify_batch_affine_dev(vrfhip_ctx* ctx, size_t n, const uin
                                             const uint8_t* d_c, const uint8_t* d_s, const uint8_t* d_ad,
                                             const uint32_t* d_ad_off, uint32_t ad_len,
                                             uint8_t* d_status, void* stream) {
-  return verify_dev_impl(ctx, n, true, d_pk_xy, d_input_xy, d_output_xy, d_c, d_s, d_ad, d_ad_off, ad_len,
+  return verify_dev_impl(ctx, n, true, d_pk_xy, d_input_xy, d_output_xy, d_c, d_s, Blob{d_ad, d_ad_off, ad_len, true},
                          d_status, stream);
 }
 int32_t vrfhip_ietf_verify_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* input,
                                  const uint8_t* output, const uint8_t* c, const uint8_t* s,
                                  const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
                                  uint8_t* status) {
-  return verify_host_impl(ctx, n, false, pk, input, output, c, s, ad, ad_off, ad_len, status);
+  return verify_host_impl(ctx, n, false, pk, input, output, c, s, Blob{ad, ad_off, ad_len, true}, status);
 }
 int32_t vrfhip_ietf_verify_batch_affine(vrfhip_ctx* ctx, size_t n, const uint8_t* pk_xy,
                                         const uint8_t* input_xy, const uint8_t* output_xy,
                                         const uint8_t* c, const uint8_t* s, const uint8_t* ad,
                                         const uint32_t* ad_off, uint32_t ad_len, uint8_t* status) {
-  return verify_host_impl(ctx, n, true, pk_xy, input_xy, output_xy, c, s, ad, ad_off, ad_len, status);
+  return verify_host_impl(ctx, n, true, pk_xy, input_xy, output_xy, c, s, Blob{ad, ad_off, ad_len, true}, status);
 }
 
 // ------------------------------------------------------------------------- key sets, keyed verification
@@ -1046,73 +1052,53 @@ int32_t vrfhip_keyset_create(vrfhip_ctx* ctx, size_t n_keys, const uint8_t* pks,
   if (n_keys > (size_t(1) << 24)) return fail(VRFHIP_ERR_BAD_ARG, "too many keys");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  vrfhip_keyset* ks = new vrfhip_keyset();
+  std::unique_ptr<vrfhip_keyset, KeysetDestroy> owner(new vrfhip_keyset());    // destroyed by every return but the last
+  vrfhip_keyset* ks = owner.get();
   ks->ctx = ctx;
   ks->n_keys = n_keys;
   if (ctx->sw) {
     // secp256r1: 33-byte Sec1 keys; per key the comb rows a challenge can reach (challenge_len + 1 rows of 128 entries)
     ks->rows = (int)ctx->desc.challenge_len + 1;
     const size_t cb = n_keys * p256::key_comb_bytes(ks->rows);
-    auto bail_sw = [&](hipError_t e, const char* what) {
-      vrfhip_keyset_destroy(ks);
-      return fail(e == hipErrorOutOfMemory ? VRFHIP_ERR_OOM : VRFHIP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    };
-    hipError_t e;
-    if ((e = hipMalloc(&ks->d_enc, n_keys * 33 + 3)) != hipSuccess) return bail_sw(e, "hipMalloc(keys)");
-    if ((e = hipMalloc(&ks->d_valid, (n_keys + 255) & ~size_t(255))) != hipSuccess) return bail_sw(e, "hipMalloc(valid)");
-    if ((e = hipMalloc(&ks->d_aff, n_keys * 18 * sizeof(uint32_t))) != hipSuccess) return bail_sw(e, "hipMalloc(affine)");
-    if ((e = hipMalloc(&ks->d_combs, cb)) != hipSuccess) return bail_sw(e, "hipMalloc(combs)");
+    HIP_TRY_AS("hipMalloc(keys)", hipMalloc(&ks->d_enc, n_keys * 33 + 3));
+    HIP_TRY_AS("hipMalloc(valid)", hipMalloc(&ks->d_valid, (n_keys + 255) & ~size_t(255)));
+    HIP_TRY_AS("hipMalloc(affine)", hipMalloc(&ks->d_aff, n_keys * 18 * sizeof(uint32_t)));
+    HIP_TRY_AS("hipMalloc(combs)", hipMalloc(&ks->d_combs, cb));
     ks->bytes = n_keys * (33 + 1 + 72) + cb;
-    if ((e = hipMemcpyAsync(ks->d_enc, pks, n_keys * 33, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return bail_sw(e, "copy keys");
+    HIP_TRY_AS("copy keys", hipMemcpyAsync(ks->d_enc, pks, n_keys * 33, hipMemcpyHostToDevice, ctx->stream));
     p256::launch_keyset_build(n_keys, ks->d_enc, ks->d_aff, ks->d_valid, ks->d_combs, ks->rows, ctx->stream);
-    if ((e = hipGetLastError()) != hipSuccess) return bail_sw(e, "launch");
+    HIP_TRY_AS("launch", hipGetLastError());
     std::vector<uint8_t> valid(n_keys);
-    if ((e = hipMemcpyAsync(valid.data(), ks->d_valid, n_keys, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return bail_sw(e, "copy back");
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail_sw(e, "synchronize");
+    HIP_TRY_AS("copy back", hipMemcpyAsync(valid.data(), ks->d_valid, n_keys, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY_AS("synchronize", hipStreamSynchronize(ctx->stream));
     if (status)
       for (size_t i = 0; i < n_keys; ++i) status[i] = valid[i] ? VRFHIP_ST_OK : VRFHIP_ST_INVALID_DATA;
-    *out = ks;
+    *out = owner.release();
     return VRFHIP_SUCCESS;
   }
   const size_t comb_bytes = n_keys * COMB_WORDS * sizeof(uint32_t);
   const size_t prefix_bytes = n_keys * COMB_ROWS * (size_t)COMB_COLS * NL * sizeof(uint32_t);
-  uint32_t *d_xy = nullptr, *d_prefix = nullptr;
-  auto bail = [&](int32_t rc) {
-    if (d_xy) (void)hipFree(d_xy);
-    if (d_prefix) (void)hipFree(d_prefix);
-    vrfhip_keyset_destroy(ks);
-    return rc;
-  };
-#define HIP_TRY_K(expr)                                                                            \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess)                                                                         \
-      return bail(fail(e__ == hipErrorOutOfMemory ? VRFHIP_ERR_OOM : VRFHIP_ERR_HIP,               \
-                       std::string(#expr) + ": " + hipGetErrorString(e__)));                       \
-  } while (0)
+  DevTmp<uint32_t> d_xy, d_prefix;
   const size_t kw = ctx->pt_bytes();                 // 32; 33 for bandersnatch_sw
-  HIP_TRY_K(hipMalloc(&ks->d_enc, n_keys * kw + 3));
-  HIP_TRY_K(hipMalloc(&ks->d_valid, (n_keys + 255) & ~size_t(255)));
-  HIP_TRY_K(hipMalloc(&ks->d_combs, comb_bytes));
-  HIP_TRY_K(hipMalloc(&d_xy, n_keys * 2 * NL * sizeof(uint32_t)));
-  HIP_TRY_K(hipMalloc(&d_prefix, prefix_bytes));
+  HIP_TRY(hipMalloc(&ks->d_enc, n_keys * kw + 3));
+  HIP_TRY(hipMalloc(&ks->d_valid, (n_keys + 255) & ~size_t(255)));
+  HIP_TRY(hipMalloc(&ks->d_combs, comb_bytes));
+  HIP_TRY(hipMalloc(&d_xy, n_keys * 2 * NL * sizeof(uint32_t)));
+  HIP_TRY(hipMalloc(&d_prefix, prefix_bytes));
   ks->bytes = n_keys * kw + n_keys + comb_bytes;
-  HIP_TRY_K(hipMemcpyAsync(ks->d_enc, pks, n_keys * kw, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ks->d_enc, pks, n_keys * kw, hipMemcpyHostToDevice, ctx->stream));
   if (ctx->bsw) launch_bsw_keyset_build(n_keys, ks->d_enc, d_xy, ks->d_valid, ks->d_combs, d_prefix, ctx->T, ctx->stream);
   else FIELD_CALL(ctx, launch_keyset_build((int)ctx->suite, n_keys, ks->d_enc, d_xy, ks->d_valid, ks->d_combs, d_prefix, ctx->T, ctx->stream));
-  HIP_TRY_K(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   if (status) {
     std::vector<uint8_t> valid(n_keys);
-    HIP_TRY_K(hipMemcpyAsync(valid.data(), ks->d_valid, n_keys, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY_K(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(valid.data(), ks->d_valid, n_keys, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < n_keys; ++i) status[i] = valid[i] ? VRFHIP_ST_OK : VRFHIP_ST_INVALID_DATA;
   } else {
-    HIP_TRY_K(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
-#undef HIP_TRY_K
-  (void)hipFree(d_xy);
-  (void)hipFree(d_prefix);
-  *out = ks;
+  *out = owner.release();
   return VRFHIP_SUCCESS;
 }
 
@@ -1136,43 +1122,41 @@ int32_t vrfhip_ietf_verify_batch_keyed_dev(vrfhip_ctx* ctx, const vrfhip_keyset*
                                            const uint8_t* d_ad, const uint32_t* d_ad_off, uint32_t ad_len,
                                            uint8_t* d_status, void* stream) {
   if (!keys) return fail(VRFHIP_ERR_BAD_ARG, "key set is NULL");
-  return verify_dev_impl(ctx, n, false, nullptr, d_input, d_output, d_c, d_s, d_ad, d_ad_off, ad_len, d_status, stream,
-                         keys, d_key_index);
+  return verify_dev_impl(ctx, n, false, nullptr, d_input, d_output, d_c, d_s, Blob{d_ad, d_ad_off, ad_len, true}, d_status,
+                         stream, keys, d_key_index);
 }
 
 int32_t vrfhip_ietf_verify_batch_keyed(vrfhip_ctx* ctx, const vrfhip_keyset* keys, size_t n,
                                        const uint32_t* key_index, const uint8_t* input, const uint8_t* output,
                                        const uint8_t* c, const uint8_t* s, const uint8_t* ad,
                                        const uint32_t* ad_off, uint32_t ad_len, uint8_t* status) {
+  const Blob h_ad{ad, ad_off, ad_len, true};
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (!keys) return fail(VRFHIP_ERR_BAD_ARG, "key set is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
   if (!key_index || !input || !output || !c || !s || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
-  if ((ad_len || ad_off) && !ad) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
-  size_t adb = blob_bytes(n, ad_off, ad_len, true);
+  if (h_ad.missing()) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
+  StagedBlob s_ad(h_ad, n);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
   const size_t pw = ctx->pt_bytes();           // input / output: 32-byte points, 33-byte Sec1 strings on secp256r1
-  size_t need = 2 * Stage::pad(n * pw) + 2 * Stage::pad(n * 32) + Stage::pad(n * 4) + Stage::pad(adb + 1) + Stage::pad((n + 1) * 4) + Stage::pad(n);
-  int32_t rc = ensure_stage(ctx, need);
-  if (rc) return rc;
-  Stage sg(ctx->d_stage);
   const uint8_t* src[4] = {input, output, c, s};
-  uint8_t* d[4];
-  for (int i = 0; i < 4; ++i) {
-    const size_t w = i < 2 ? pw : 32;
-    d[i] = sg.take(n * w);
-    HIP_TRY(hipMemcpyAsync(d[i], src[i], n * w, hipMemcpyHostToDevice, ctx->stream));
-  }
-  uint32_t* d_idx = reinterpret_cast<uint32_t*>(sg.take(n * 4));
-  uint8_t* d_ad = sg.take(adb + 1);
-  uint32_t* d_off = reinterpret_cast<uint32_t*>(sg.take((n + 1) * 4));
-  uint8_t* d_st = sg.take(n);
+  const size_t w[4] = {pw, pw, 32, 32};
+  uint8_t *d[4], *d_idx, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
+    for (int i = 0; i < 4; ++i) d[i] = sg.take(n * w[i]);
+    d_idx = sg.take(n * 4);
+    s_ad.take(sg);
+    d_st = sg.take(n);
+  });
+  if (rc) return rc;
+  for (int i = 0; i < 4; ++i) HIP_TRY(hipMemcpyAsync(d[i], src[i], n * w[i], hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(d_idx, key_index, n * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (adb) HIP_TRY(hipMemcpyAsync(d_ad, ad, adb, hipMemcpyHostToDevice, ctx->stream));
-  if (ad_off) HIP_TRY(hipMemcpyAsync(d_off, ad_off, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  rc = vrfhip_ietf_verify_batch_keyed_dev(ctx, keys, n, d_idx, d[0], d[1], d[2], d[3], d_ad, ad_off ? d_off : nullptr,
-                                          ad_len, d_st, ctx->stream);
+  Blob d_ad;
+  rc = stage_blob(ctx, s_ad, &d_ad);
+  if (rc) return rc;
+  rc = vrfhip_ietf_verify_batch_keyed_dev(ctx, keys, n, reinterpret_cast<uint32_t*>(d_idx), d[0], d[1], d[2], d[3], d_ad.p,
+                                          d_ad.off, ad_len, d_st, ctx->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1187,76 +1171,57 @@ struct ProveOut {
   uint8_t *output, *c, *s, *pk, *input, *status;
   uint8_t *r, *ok, *sb, *blinding;     // Pedersen only
 };
-int32_t prove_dev_impl(vrfhip_ctx* ctx, size_t n, bool pedersen, const uint8_t* d_sk,
-                       const uint8_t* d_msg, const uint32_t* d_msg_off, uint32_t msg_len,
-                       const uint8_t* d_input, const uint8_t* d_ad, const uint32_t* d_ad_off,
-                       uint32_t ad_len, const ProveOut& o, void* stream) {
+int32_t prove_dev_impl(vrfhip_ctx* ctx, size_t n, bool pedersen, const uint8_t* d_sk, const Blob& msg, const uint8_t* d_input,
+                       const Blob& ad, const ProveOut& o, void* stream) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
   if (!d_sk || !o.output || !o.s) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   if (pedersen ? (!o.pk || !o.r || !o.ok || !o.sb) : !o.c) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
-  if (!d_input && !d_msg && (msg_len || d_msg_off)) return fail(VRFHIP_ERR_BAD_ARG, "msg is NULL");
-  if ((ad_len || d_ad_off) && !d_ad) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
+  if (!d_input && msg.missing()) return fail(VRFHIP_ERR_BAD_ARG, "msg is NULL");
+  if (ad.missing()) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
   if (pedersen && !ctx->has_pedersen()) return fail(VRFHIP_ERR_UNSUPPORTED, NO_BLINDING_MSG);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
   int32_t rc = ensure_workspace(ctx, n);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  auto at = [](uint8_t* p, size_t base, size_t w) -> uint8_t* { return p ? p + base * w : nullptr; };
-  if (ctx->sw) {
-    for (size_t base = 0; base < n; base += ctx->ws_cap) {
-      const size_t m = std::min(ctx->ws_cap, n - base);
-      p256::ProveArgs a;
+  // point outputs: compressed (32 / 33 bytes) or x || y (64: VRFHIP_FLAG_PROVE_POINTS_AFFINE); input points and enc(H) out are
+  // always compressed
+  const size_t ptw = ctx->prove_point_bytes(), ipw = ctx->pt_bytes();
+  rc = for_chunks(n, ctx->ws_cap, [&](size_t base, size_t m) -> int32_t {
+    auto common = [&](auto& a) {
       a.n = m;
       a.sk = d_sk + base * 32;
-      if (d_msg_off) a.msg = make_view(d_msg, d_msg_off + base, 0, false);
-      else a.msg = make_view(d_msg ? d_msg + base * (size_t)msg_len : nullptr, nullptr, msg_len, false);
-      a.h_given = d_input ? d_input + base * 33 : nullptr;
-      a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
-      const size_t ptw = ctx->prove_point_bytes();       // 33: Sec1, 64: x || y (VRFHIP_FLAG_PROVE_POINTS_AFFINE)
-      a.out_affine = ptw == 64 ? (ctx->coords_mont256() ? 2 : 1) : 0;
+      a.msg = msg.view(base);
+      a.h_given = at(d_input, base, ipw);
+      a.ad = ad.view(base);
       a.gamma = at(o.output, base, ptw); a.c = at(o.c, base, 32); a.s = at(o.s, base, 32);
-      a.pk_out = at(o.pk, base, ptw); a.h_out = at(o.input, base, 33); a.status = at(o.status, base, 1);
+      a.pk_out = at(o.pk, base, ptw); a.h_out = at(o.input, base, ipw); a.status = at(o.status, base, 1);
       a.pedersen = pedersen ? 1 : 0;
-      a.ct_tables = (ctx->flags & VRFHIP_FLAG_CT_TABLES) ? 1 : 0;
       a.r_out = at(o.r, base, ptw); a.ok_out = at(o.ok, base, ptw); a.sb_out = at(o.sb, base, 32);
       a.blinding_out = at(o.blinding, base, 32);
-      a.comb_b = ctx->d_p256_comb_b;
       a.tai_queue = ctx->d_queue;
+    };
+    if (ctx->sw) {
+      p256::ProveArgs a{};
+      common(a);
+      a.out_affine = ctx->affine_in(ptw == 64);            // the kernel writes Montgomery-256 coordinates itself
+      a.ct_tables = (ctx->flags & VRFHIP_FLAG_CT_TABLES) ? 1 : 0;
+      a.comb_b = ctx->d_p256_comb_b;
       a.ws = ctx->p256_ws;
       a.comb = ctx->d_p256_comb;
       a.str = ctx->T.sq.str;
       p256::launch_prove(a, st, prof_events(ctx));
       // sk and the nonce k of these items lay in the scalar region: nothing secret outlives the call in device memory
       HIP_TRY(hipMemsetAsync(ctx->p256_ws.sc, 0, ctx->p256_ws.cap * p256::WS_SC_WORDS * sizeof(uint32_t), st));
+      return VRFHIP_SUCCESS;
     }
-    HIP_TRY(hipGetLastError());
-    return VRFHIP_SUCCESS;
-  }
-  const size_t ipw = ctx->pt_bytes();                    // input points and enc(H) out: always compressed
-  for (size_t base = 0; base < n; base += ctx->ws_cap) {
-    size_t m = std::min(ctx->ws_cap, n - base);
-    ProveArgs a;
+    ProveArgs a{};
+    common(a);
     a.suite = (int)ctx->suite;
     a.k_lane = ctx->dbg_prove_k > 0 ? ctx->dbg_prove_k : lanes_k(m, PROVE_K);
-    a.n = m;
-    a.sk = d_sk + base * 32;
-    if (d_msg_off) a.msg = make_view(d_msg, d_msg_off + base, 0, false);
-    else a.msg = make_view(d_msg ? d_msg + base * (size_t)msg_len : nullptr, nullptr, msg_len, false);
-    a.h_given = d_input ? d_input + base * ipw : nullptr;
-    a.tai_queue = ctx->d_queue;
-    a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
-    const size_t ptw = ctx->prove_point_bytes();        // 32: compressed, 64: x || y (VRFHIP_FLAG_PROVE_POINTS_AFFINE)
     a.out_affine = ptw == 64 ? 1 : 0;
-    a.gamma = at(o.output, base, ptw); a.c = at(o.c, base, 32); a.s = at(o.s, base, 32);
-    a.pk_out = at(o.pk, base, ptw);
-    a.h_out = at(o.input, base, ipw);
-    a.status = at(o.status, base, 1);
-    a.pedersen = pedersen ? 1 : 0;
     a.check_mask = ctx->check_mask() | ((ctx->flags & VRFHIP_FLAG_CT_TABLES) ? (uint32_t)CHK_CT_TABLES : 0u);
-    a.r_out = at(o.r, base, ptw); a.ok_out = at(o.ok, base, ptw); a.sb_out = at(o.sb, base, 32);
-    a.blinding_out = at(o.blinding, base, 32);
     a.ws = ctx->ws;
     a.T = ctx->T;
     if (ctx->bsw) launch_bsw_prove(a, st, prof_events(ctx));
@@ -1269,51 +1234,45 @@ int32_t prove_dev_impl(vrfhip_ctx* ctx, size_t n, bool pedersen, const uint8_t* 
     // the aux region held the nonces k, kb and the blinding factor b of these items: wipe it (the reference's
     // `Secret` zeroizes on drop; nothing secret may outlive the call in device memory)
     HIP_TRY(hipMemsetAsync(ctx->ws.aux, 0, m * AUX_WORDS * sizeof(uint32_t), st));
-  }
+    return VRFHIP_SUCCESS;
+  });
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return VRFHIP_SUCCESS;
 }
 
 // host-pointer form shared by the IETF and Pedersen provers
-int32_t prove_host_impl(vrfhip_ctx* ctx, size_t n, bool pedersen, const uint8_t* sk, const uint8_t* msg,
-                        const uint32_t* msg_off, uint32_t msg_len, const uint8_t* input,
-                        const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len, const ProveOut& h) {
+int32_t prove_host_impl(vrfhip_ctx* ctx, size_t n, bool pedersen, const uint8_t* sk, const Blob& msg, const uint8_t* input,
+                        const Blob& ad, const ProveOut& h) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
   if (!sk || !h.output || !h.s) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   if (pedersen ? (!h.pk || !h.r || !h.ok || !h.sb) : !h.c) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
-  if (!input && !msg && (msg_len || msg_off)) return fail(VRFHIP_ERR_BAD_ARG, "msg is NULL");
-  if ((ad_len || ad_off) && !ad) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
-  size_t adb = blob_bytes(n, ad_off, ad_len, true);
-  size_t msgb = input ? 0 : blob_bytes(n, msg_off, msg_len, false);
+  if (!input && msg.missing()) return fail(VRFHIP_ERR_BAD_ARG, "msg is NULL");
+  if (ad.missing()) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
+  // a given input point replaces the message: nothing of it is read or sent
+  StagedBlob s_msg(input ? Blob{nullptr, nullptr, msg.len, false} : msg, n), s_ad(ad, n);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
   const size_t ptw = ctx->prove_point_bytes(), ipw = ctx->pt_bytes();     // outputs (maybe x || y) and input points
-  size_t need = 5 * Stage::pad(n * 32) + 2 * Stage::pad(n * ipw) + 4 * Stage::pad(n * ptw) + Stage::pad(msgb + 1) + Stage::pad(adb + 1) +
-                2 * Stage::pad((n + 1) * 4) + Stage::pad(n);
-  int32_t rc = ensure_stage(ctx, need);
-  if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t* d_sk = sg.take(n * 32);
-  uint8_t* d_in = sg.take(n * ipw);
+  uint8_t *d_sk, *d_in;
   ProveOut d{};
-  d.output = sg.take(n * ptw); d.c = sg.take(n * 32); d.s = sg.take(n * 32);
-  d.pk = sg.take(n * ptw); d.input = sg.take(n * ipw);
-  d.r = sg.take(n * ptw); d.ok = sg.take(n * ptw); d.sb = sg.take(n * 32); d.blinding = sg.take(n * 32);
-  uint8_t* d_msg = sg.take(msgb + 1);
-  uint8_t* d_ad = sg.take(adb + 1);
-  uint32_t* d_moff = reinterpret_cast<uint32_t*>(sg.take((n + 1) * 4));
-  uint32_t* d_aoff = reinterpret_cast<uint32_t*>(sg.take((n + 1) * 4));
-  d.status = sg.take(n);
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
+    d_sk = sg.take(n * 32);
+    d_in = sg.take(n * ipw);
+    d.output = sg.take(n * ptw); d.c = sg.take(n * 32); d.s = sg.take(n * 32);
+    d.pk = sg.take(n * ptw); d.input = sg.take(n * ipw);
+    d.r = sg.take(n * ptw); d.ok = sg.take(n * ptw); d.sb = sg.take(n * 32); d.blinding = sg.take(n * 32);
+    s_msg.take(sg);
+    s_ad.take(sg);
+    d.status = sg.take(n);
+  });
+  if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(d_sk, sk, n * 32, hipMemcpyHostToDevice, ctx->stream));
   if (input) HIP_TRY(hipMemcpyAsync(d_in, input, n * ipw, hipMemcpyHostToDevice, ctx->stream));
-  if (msgb) HIP_TRY(hipMemcpyAsync(d_msg, msg, msgb, hipMemcpyHostToDevice, ctx->stream));
-  if (adb) HIP_TRY(hipMemcpyAsync(d_ad, ad, adb, hipMemcpyHostToDevice, ctx->stream));
-  if (msg_off && !input)
-    HIP_TRY(hipMemcpyAsync(d_moff, msg_off, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (ad_off) HIP_TRY(hipMemcpyAsync(d_aoff, ad_off, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  rc = prove_dev_impl(ctx, n, pedersen, d_sk, d_msg, (msg_off && !input) ? d_moff : nullptr, msg_len,
-                      input ? d_in : nullptr, d_ad, ad_off ? d_aoff : nullptr, ad_len, d, ctx->stream);
+  Blob d_msg, d_ad;
+  if ((rc = stage_blob(ctx, s_msg, &d_msg)) || (rc = stage_blob(ctx, s_ad, &d_ad))) return rc;
+  rc = prove_dev_impl(ctx, n, pedersen, d_sk, d_msg, input ? d_in : nullptr, d_ad, d, ctx->stream);
   if (rc) return rc;
   auto back = [&](uint8_t* dst, const uint8_t* src, size_t bytes) -> hipError_t {
     return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
@@ -1348,7 +1307,7 @@ int32_t vrfhip_ietf_prove_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_
                                     uint8_t* d_input_out, uint8_t* d_status, void* stream) {
   ProveOut o{};
   o.output = d_output; o.c = d_c; o.s = d_s; o.pk = d_pk_out; o.input = d_input_out; o.status = d_status;
-  return prove_dev_impl(ctx, n, false, d_sk, d_msg, d_msg_off, msg_len, d_input, d_ad, d_ad_off, ad_len, o,
+  return prove_dev_impl(ctx, n, false, d_sk, Blob{d_msg, d_msg_off, msg_len, false}, d_input, Blob{d_ad, d_ad_off, ad_len, true}, o,
                         stream);
 }
 
@@ -1363,7 +1322,7 @@ int32_t vrfhip_pedersen_prove_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t
   ProveOut o{};
   o.output = d_output; o.s = d_s; o.pk = d_pk_com; o.input = d_input_out; o.status = d_status;
   o.r = d_r; o.ok = d_ok; o.sb = d_sb; o.blinding = d_blinding_out;
-  return prove_dev_impl(ctx, n, true, d_sk, d_msg, d_msg_off, msg_len, d_input, d_ad, d_ad_off, ad_len, o,
+  return prove_dev_impl(ctx, n, true, d_sk, Blob{d_msg, d_msg_off, msg_len, false}, d_input, Blob{d_ad, d_ad_off, ad_len, true}, o,
                         stream);
 }
 
@@ -1374,7 +1333,7 @@ int32_t vrfhip_ietf_prove_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* sk, co
                                 uint8_t* input_out, uint8_t* status) {
   ProveOut h{};
   h.output = output; h.c = c; h.s = s; h.pk = pk_out; h.input = input_out; h.status = status;
-  return prove_host_impl(ctx, n, false, sk, msg, msg_off, msg_len, input, ad, ad_off, ad_len, h);
+  return prove_host_impl(ctx, n, false, sk, Blob{msg, msg_off, msg_len, false}, input, Blob{ad, ad_off, ad_len, true}, h);
 }
 
 int32_t vrfhip_pedersen_prove_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* sk, const uint8_t* msg,
@@ -1386,100 +1345,106 @@ int32_t vrfhip_pedersen_prove_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* sk
   ProveOut h{};
   h.output = output; h.s = s; h.pk = pk_com; h.input = input_out; h.status = status;
   h.r = r; h.ok = ok; h.sb = sb; h.blinding = blinding_out;
-  return prove_host_impl(ctx, n, true, sk, msg, msg_off, msg_len, input, ad, ad_off, ad_len, h);
+  return prove_host_impl(ctx, n, true, sk, Blob{msg, msg_off, msg_len, false}, input, Blob{ad, ad_off, ad_len, true}, h);
 }
 
 // ------------------------------------------------------------------------- Pedersen verify
 }  // extern "C"
 
 namespace {
+// the arrays of a batch of Pedersen proofs: five point arrays (pw bytes per item) and the two responses (32)
+struct PedIn {
+  const uint8_t *h, *gamma, *pk_com, *r, *ok, *s, *sb;
+  bool any_null() const { return !h || !gamma || !pk_com || !r || !ok || !s || !sb; }
+  // the arrays from item `base` on
+  PedIn from(size_t base, size_t pw) const {
+    return PedIn{h + base * pw, gamma + base * pw, pk_com + base * pw, r + base * pw, ok + base * pw, s + base * 32, sb + base * 32};
+  }
+  template <class A>
+  void put(A& a) const {
+    a.h = h; a.gamma = gamma; a.pk_com = pk_com; a.r = r; a.ok = ok; a.s = s; a.sb = sb;
+  }
+};
+// host arrays -> staging: the layout (take) and the copies (send) of the seven arrays
+struct PedStage {
+  uint8_t* d[7];
+  void take(Stage& sg, size_t n, size_t pw) {
+    for (int i = 0; i < 7; ++i) d[i] = sg.take(n * (i < 5 ? pw : 32));
+  }
+  int32_t send(vrfhip_ctx* ctx, const PedIn& in, size_t n, size_t pw) const {
+    const uint8_t* src[7] = {in.h, in.gamma, in.pk_com, in.r, in.ok, in.s, in.sb};
+    for (int i = 0; i < 7; ++i) HIP_TRY(hipMemcpyAsync(d[i], src[i], n * (i < 5 ? pw : 32), hipMemcpyHostToDevice, ctx->stream));
+    return VRFHIP_SUCCESS;
+  }
+  PedIn dev() const { return PedIn{d[0], d[1], d[2], d[3], d[4], d[5], d[6]}; }
+};
+
 // affine: the five point arrays are 64-byte x || y (canonical, or Montgomery-256 under VRFHIP_FLAG_COORDS_MONT256)
-int32_t ped_verify_dev_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* d_input, const uint8_t* d_output,
-                            const uint8_t* d_pk_com, const uint8_t* d_r, const uint8_t* d_ok, const uint8_t* d_s,
-                            const uint8_t* d_sb, const uint8_t* d_ad, const uint32_t* d_ad_off, uint32_t ad_len,
-                            uint8_t* d_status, void* stream) {
+int32_t ped_verify_dev_impl(vrfhip_ctx* ctx, size_t n, bool affine, const PedIn& in, const Blob& ad, uint8_t* d_status,
+                            void* stream) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
-  if (!d_input || !d_output || !d_pk_com || !d_r || !d_ok || !d_s || !d_sb || !d_status)
-    return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
-  if ((ad_len || d_ad_off) && !d_ad) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
+  if (in.any_null() || !d_status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  if (ad.missing()) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
   if (!ctx->has_pedersen()) return fail(VRFHIP_ERR_UNSUPPORTED, NO_BLINDING_MSG);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
   int32_t rc = ensure_workspace(ctx, n);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int affine_in = affine ? (ctx->coords_mont256() ? 2 : 1) : 0;
-  if (ctx->sw) {
-    const size_t pw = affine ? 64 : 33;
-    for (size_t base = 0; base < n; base += ctx->ws_cap) {
-      const size_t m = std::min(ctx->ws_cap, n - base);
-      p256::PedVerifyArgs a;
+  const size_t pw = affine ? 64 : ctx->pt_bytes();
+  rc = for_chunks(n, ctx->ws_cap, [&](size_t base, size_t m) -> int32_t {
+    auto common = [&](auto& a) {
       a.n = m;
-      a.h = d_input + base * pw; a.gamma = d_output + base * pw; a.pk_com = d_pk_com + base * pw;
-      a.r = d_r + base * pw; a.ok = d_ok + base * pw; a.s = d_s + base * 32; a.sb = d_sb + base * 32;
-      a.affine_in = affine_in;
-      a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
+      in.from(base, pw).put(a);
+      a.affine_in = ctx->affine_in(affine);
+      a.ad = ad.view(base);
       a.status = d_status + base;
+    };
+    if (ctx->sw) {
+      p256::PedVerifyArgs a{};
+      common(a);
       a.ws = ctx->p256_ws;
       a.comb = ctx->d_p256_comb; a.comb_b = ctx->d_p256_comb_b;
       a.str = ctx->T.sq.str;
       p256::launch_pedersen_verify(a, st, prof_events(ctx));
+      return VRFHIP_SUCCESS;
     }
-    HIP_TRY(hipGetLastError());
-    return VRFHIP_SUCCESS;
-  }
-  const size_t pw = affine ? 64 : ctx->pt_bytes();
-  for (size_t base = 0; base < n; base += ctx->ws_cap) {
-    size_t m = std::min(ctx->ws_cap, n - base);
-    PedersenVerifyArgs a;
+    PedersenVerifyArgs a{};
+    common(a);
     a.suite = (int)ctx->suite;
-    a.n = m;
-    a.h = d_input + base * pw; a.gamma = d_output + base * pw; a.pk_com = d_pk_com + base * pw;
-    a.r = d_r + base * pw; a.ok = d_ok + base * pw; a.s = d_s + base * 32; a.sb = d_sb + base * 32;
-    a.affine_in = affine_in;
-    a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
     a.check_mask = ctx->check_mask();
-    a.status = d_status + base;
     a.ws = ctx->ws;
     a.T = ctx->T;
     if (ctx->bsw) launch_bsw_pedersen_verify(a, st, prof_events(ctx));
     else FIELD_CALL(ctx, launch_pedersen_verify(a, st, prof_events(ctx)));
-  }
+    return VRFHIP_SUCCESS;
+  });
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return VRFHIP_SUCCESS;
 }
 
-int32_t ped_verify_host_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* input, const uint8_t* output,
-                             const uint8_t* pk_com, const uint8_t* r, const uint8_t* ok, const uint8_t* s, const uint8_t* sb,
-                             const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len, uint8_t* status) {
+int32_t ped_verify_host_impl(vrfhip_ctx* ctx, size_t n, bool affine, const PedIn& in, const Blob& ad, uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
-  if (!input || !output || !pk_com || !r || !ok || !s || !sb || !status)
-    return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
-  if ((ad_len || ad_off) && !ad) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
-  size_t adb = blob_bytes(n, ad_off, ad_len, true);
+  if (in.any_null() || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  if (ad.missing()) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
+  StagedBlob s_ad(ad, n);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
   const size_t pw = affine ? 64 : ctx->pt_bytes();
-  size_t need = 5 * Stage::pad(n * pw) + 2 * Stage::pad(n * 32) + Stage::pad(adb + 1) + Stage::pad((n + 1) * 4) + Stage::pad(n);
-  int32_t rc = ensure_stage(ctx, need);
+  PedStage d;
+  uint8_t* d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
+    d.take(sg, n, pw);
+    s_ad.take(sg);
+    d_st = sg.take(n);
+  });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  const uint8_t* src[7] = {input, output, pk_com, r, ok, s, sb};
-  uint8_t* d[7];
-  for (int i = 0; i < 7; ++i) {
-    const size_t w = i < 5 ? pw : 32;
-    d[i] = sg.take(n * w);
-    HIP_TRY(hipMemcpyAsync(d[i], src[i], n * w, hipMemcpyHostToDevice, ctx->stream));
-  }
-  uint8_t* d_ad = sg.take(adb + 1);
-  uint32_t* d_off = reinterpret_cast<uint32_t*>(sg.take((n + 1) * 4));
-  uint8_t* d_st = sg.take(n);
-  if (adb) HIP_TRY(hipMemcpyAsync(d_ad, ad, adb, hipMemcpyHostToDevice, ctx->stream));
-  if (ad_off) HIP_TRY(hipMemcpyAsync(d_off, ad_off, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  rc = ped_verify_dev_impl(ctx, n, affine, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d_ad, ad_off ? d_off : nullptr, ad_len,
-                           d_st, ctx->stream);
+  Blob d_ad;
+  if ((rc = d.send(ctx, in, n, pw)) || (rc = stage_blob(ctx, s_ad, &d_ad))) return rc;
+  rc = ped_verify_dev_impl(ctx, n, affine, d.dev(), d_ad, d_st, ctx->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1495,8 +1460,8 @@ int32_t vrfhip_pedersen_verify_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_
                                          const uint8_t* d_sb, const uint8_t* d_ad,
                                          const uint32_t* d_ad_off, uint32_t ad_len,
                                          uint8_t* d_status, void* stream) {
-  return ped_verify_dev_impl(ctx, n, false, d_input, d_output, d_pk_com, d_r, d_ok, d_s, d_sb, d_ad, d_ad_off, ad_len,
-                             d_status, stream);
+  return ped_verify_dev_impl(ctx, n, false, PedIn{d_input, d_output, d_pk_com, d_r, d_ok, d_s, d_sb},
+                             Blob{d_ad, d_ad_off, ad_len, true}, d_status, stream);
 }
 int32_t vrfhip_pedersen_verify_batch_affine_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_input_xy,
                                                 const uint8_t* d_output_xy, const uint8_t* d_pk_com_xy,
@@ -1504,8 +1469,8 @@ int32_t vrfhip_pedersen_verify_batch_affine_dev(vrfhip_ctx* ctx, size_t n, const
                                                 const uint8_t* d_sb, const uint8_t* d_ad,
                                                 const uint32_t* d_ad_off, uint32_t ad_len,
                                                 uint8_t* d_status, void* stream) {
-  return ped_verify_dev_impl(ctx, n, true, d_input_xy, d_output_xy, d_pk_com_xy, d_r_xy, d_ok_xy, d_s, d_sb, d_ad, d_ad_off,
-                             ad_len, d_status, stream);
+  return ped_verify_dev_impl(ctx, n, true, PedIn{d_input_xy, d_output_xy, d_pk_com_xy, d_r_xy, d_ok_xy, d_s, d_sb},
+                             Blob{d_ad, d_ad_off, ad_len, true}, d_status, stream);
 }
 
 int32_t vrfhip_pedersen_verify_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* input,
@@ -1513,162 +1478,124 @@ int32_t vrfhip_pedersen_verify_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* i
                                      const uint8_t* ok, const uint8_t* s, const uint8_t* sb,
                                      const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
                                      uint8_t* status) {
-  return ped_verify_host_impl(ctx, n, false, input, output, pk_com, r, ok, s, sb, ad, ad_off, ad_len, status);
+  return ped_verify_host_impl(ctx, n, false, PedIn{input, output, pk_com, r, ok, s, sb}, Blob{ad, ad_off, ad_len, true}, status);
 }
 int32_t vrfhip_pedersen_verify_batch_affine(vrfhip_ctx* ctx, size_t n, const uint8_t* input_xy,
                                             const uint8_t* output_xy, const uint8_t* pk_com_xy, const uint8_t* r_xy,
                                             const uint8_t* ok_xy, const uint8_t* s, const uint8_t* sb,
                                             const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
                                             uint8_t* status) {
-  return ped_verify_host_impl(ctx, n, true, input_xy, output_xy, pk_com_xy, r_xy, ok_xy, s, sb, ad, ad_off, ad_len, status);
+  return ped_verify_host_impl(ctx, n, true, PedIn{input_xy, output_xy, pk_com_xy, r_xy, ok_xy, s, sb},
+                              Blob{ad, ad_off, ad_len, true}, status);
 }
 
 // ------------------------------------------------------------------------- Pedersen verify, batched (RLC)
 }  // extern "C"
 namespace {
-int32_t rlc_dev_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* d_input,
-                     const uint8_t* d_output, const uint8_t* d_pk_com,
-                     const uint8_t* d_r, const uint8_t* d_ok, const uint8_t* d_s,
-                     const uint8_t* d_sb, const uint8_t* d_ad,
-                     const uint32_t* d_ad_off, uint32_t ad_len,
-                     const uint8_t seed[32], uint8_t* d_status,
-                     uint8_t* d_fail_flag, void* stream) {
+int32_t rlc_dev_impl(vrfhip_ctx* ctx, size_t n, bool affine, const PedIn& in, const Blob& ad, const uint8_t seed[32],
+                     uint8_t* d_status, uint8_t* d_fail_flag, void* stream) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (!d_fail_flag || !seed) return fail(VRFHIP_ERR_BAD_ARG, "NULL fail flag or seed");
-  if (n && (!d_input || !d_output || !d_pk_com || !d_r || !d_ok || !d_s || !d_sb || !d_status))
-    return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
-  if ((ad_len || d_ad_off) && !d_ad) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
+  if (n && (in.any_null() || !d_status)) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  if (ad.missing()) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
   if (!ctx->has_pedersen()) return fail(VRFHIP_ERR_UNSUPPORTED, NO_BLINDING_MSG);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   HIP_TRY(hipMemsetAsync(d_fail_flag, 0, 1, st));
   if (n == 0) return VRFHIP_SUCCESS;
-  if (ctx->sw) {
-    // secp256r1: launch groups of at most 2^20 proofs, each ONE MSM over 5 m + 2 points; no per-proof workspace at all
-    const size_t cap = std::min<size_t>(n, size_t(1) << 20);
-    const size_t Ncap = 5 * cap + 2;
-    auto p256_groups = [&](size_t N_, size_t long_) {
-      int g = ctx->dbg_p256_msm_groups > 0 ? ctx->dbg_p256_msm_groups : p256::msm_groups(N_, long_, ctx->cus);
-      const size_t min_g = (N_ + (size_t(1) << 21) - 1) >> 21;
-      return (size_t)g < min_g ? (int)min_g : g;
-    };
-    const int groups_cap = p256_groups(Ncap, 3 * cap + 2);
-    const size_t msm_b = Stage::pad(p256::msm_workspace_bytes(Ncap, groups_cap));
-    int32_t rc2 = ensure_msm_workspace(ctx, msm_b + Stage::pad(digest_ws_bytes(cap)) + 256);
-    if (rc2) return rc2;
-    uint8_t* d_dws = static_cast<uint8_t*>(ctx->d_msm_ws) + msm_b;
-    uint8_t* d_rt = d_dws + Stage::pad(digest_ws_bytes(cap));
-    for (size_t base = 0; base < n; base += cap) {
-      const size_t m = std::min(cap, n - base), N = 5 * m + 2;
-      p256::RlcArgs a{};
+  // A launch group is ONE MSM over 5 m + 2 points.  secp256r1: groups of at most 2^20 proofs, no per-proof workspace at
+  // all; the others: groups of ws_cap.  The MSM workspace holds MSM | digest tree | root, sized for the largest group.
+  auto p256_groups = [&](size_t N_, size_t long_) {
+    int g = ctx->dbg_p256_msm_groups > 0 ? ctx->dbg_p256_msm_groups : p256::msm_groups(N_, long_, ctx->cus);
+    const size_t min_g = (N_ + (size_t(1) << 21) - 1) >> 21;
+    return (size_t)g < min_g ? (int)min_g : g;
+  };
+  int32_t rc = ctx->sw ? VRFHIP_SUCCESS : ensure_workspace(ctx, n);
+  if (rc) return rc;
+  const size_t cap = std::min(n, ctx->sw ? size_t(1) << 20 : ctx->ws_cap), Ncap = 5 * cap + 2;
+  const size_t msm_b = Stage::pad(ctx->sw ? p256::msm_workspace_bytes(Ncap, p256_groups(Ncap, 3 * cap + 2))
+                                          : msm_workspace_bytes(Ncap, msm_groups(Ncap, 3 * cap + 2, ctx->cus)));
+  rc = ensure_msm_workspace(ctx, msm_b + Stage::pad(digest_ws_bytes(cap)) + 256);
+  if (rc) return rc;
+  uint8_t* d_digest_ws = static_cast<uint8_t*>(ctx->d_msm_ws) + msm_b;
+  uint8_t* d_root = d_digest_ws + Stage::pad(digest_ws_bytes(cap));
+  const size_t pw = affine ? 64 : ctx->pt_bytes();
+  rc = for_chunks(n, cap, [&](size_t base, size_t m) -> int32_t {
+    const size_t N = 5 * m + 2;
+    const PedIn c = in.from(base, pw);
+    // the weights of this launch group depend on every input byte of the group (digest.cuh)
+    DigestSrc ds{};
+    const uint8_t* arr[7] = {c.h, c.gamma, c.pk_com, c.r, c.ok, c.s, c.sb};
+    for (int j = 0; j < 7; ++j) { ds.p[j] = arr[j]; ds.w[j] = j < 5 ? (uint32_t)pw : 32u; }
+    ds.n_arr = 7;
+    ds.ad = ad.view(base);
+    launch_batch_digest(ds, m, base, d_digest_ws, d_root, st);
+    auto common = [&](auto& a) {
       a.n = m;
       a.index0 = base;
-      const size_t pw = affine ? 64 : 33;
-      a.h = d_input + base * pw; a.gamma = d_output + base * pw; a.pk_com = d_pk_com + base * pw;
-      a.r = d_r + base * pw; a.ok = d_ok + base * pw; a.s = d_s + base * 32; a.sb = d_sb + base * 32;
-      a.affine_in = affine ? (ctx->coords_mont256() ? 2 : 1) : 0;
-      a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
+      c.put(a);
+      a.affine_in = ctx->affine_in(affine);
+      a.ad = ds.ad;
       a.status = d_status + base;
-      a.L = p256::msm_layout(N, 3 * m + 2, p256_groups(N, 3 * m + 2), ctx->d_msm_ws);
       std::memcpy(a.seed, seed, 32);
+      a.root = d_root;
+    };
+    if (ctx->sw) {
+      p256::RlcArgs a{};
+      common(a);
+      a.L = p256::msm_layout(N, 3 * m + 2, p256_groups(N, 3 * m + 2), ctx->d_msm_ws);
       std::memcpy(a.gen_xy, ctx->desc.generator, 64);
       std::memcpy(a.b_xy, ctx->desc.blinding_base, 64);
       a.str = ctx->T.sq.str;
-      DigestSrc ds{};
-      const uint8_t* arr[7] = {a.h, a.gamma, a.pk_com, a.r, a.ok, a.s, a.sb};
-      for (int j = 0; j < 7; ++j) { ds.p[j] = arr[j]; ds.w[j] = j < 5 ? (uint32_t)pw : 32u; }
-      ds.n_arr = 7;
-      ds.ad = a.ad;
-      launch_batch_digest(ds, m, base, d_dws, d_rt, st);
-      a.root = d_rt;
       p256::launch_pedersen_rlc(a, d_fail_flag, st, prof_events(ctx));
+      return VRFHIP_SUCCESS;
     }
-    HIP_TRY(hipGetLastError());
-    return VRFHIP_SUCCESS;
-  }
-  int32_t rc = ensure_workspace(ctx, n);
-  if (rc) return rc;
-  size_t msm_bytes;
-  {
-    size_t m = std::min(ctx->ws_cap, n), N = 5 * m + 2;
-    msm_bytes = Stage::pad(msm_workspace_bytes(N, msm_groups(N, 3 * m + 2, ctx->cus)));
-    rc = ensure_msm_workspace(ctx, msm_bytes + Stage::pad(digest_ws_bytes(m)) + 256);   // MSM | digest tree | root
-    if (rc) return rc;
-  }
-  uint8_t* d_digest_ws = static_cast<uint8_t*>(ctx->d_msm_ws) + msm_bytes;
-  uint8_t* d_root = d_digest_ws + Stage::pad(digest_ws_bytes(std::min(ctx->ws_cap, n)));
-  for (size_t base = 0; base < n; base += ctx->ws_cap) {
-    size_t m = std::min(ctx->ws_cap, n - base), N = 5 * m + 2;
-    RlcArgs a;
+    RlcArgs a{};
+    common(a);
     a.suite = (int)ctx->suite;
     a.k_lane = lanes_k(m, VERIFY_K_POLICY);
-    a.n = m;
-    a.index0 = base;
-    const size_t pw = affine ? 64 : ctx->pt_bytes();
-    a.h = d_input + base * pw; a.gamma = d_output + base * pw; a.pk_com = d_pk_com + base * pw;
-    a.r = d_r + base * pw; a.ok = d_ok + base * pw; a.s = d_s + base * 32; a.sb = d_sb + base * 32;
-    a.affine_in = affine ? (ctx->coords_mont256() ? 2 : 1) : 0;
     a.check_mask = ctx->check_mask();
-    a.ad = make_view(d_ad, d_ad_off ? d_ad_off + base : nullptr, ad_len, true);
-    a.status = d_status + base;
     a.scratch = ctx->ws.tabs;
     a.scratch_stride = WS_TABS * WIN_TABLE_WORDS;
     a.L = msm_layout(N, 3 * m + 2, msm_groups(N, 3 * m + 2, ctx->cus), ctx->d_msm_ws);
     a.fixed_cols = reinterpret_cast<uint64_t*>(a.L.flags + 128);
     a.T = ctx->T;
-    std::memcpy(a.seed, seed, 32);
-    // the weights of this launch group depend on every input byte of the group (digest.cuh)
-    DigestSrc ds{};
-    const uint8_t* arr[7] = {a.h, a.gamma, a.pk_com, a.r, a.ok, a.s, a.sb};
-    for (int j = 0; j < 7; ++j) { ds.p[j] = arr[j]; ds.w[j] = j < 5 ? (uint32_t)pw : 32u; }
-    ds.n_arr = 7;
-    ds.ad = a.ad;
-    launch_batch_digest(ds, m, base, d_digest_ws, d_root, st);
-    a.root = d_root;
     if (ctx->bsw) launch_bsw_pedersen_rlc(a, d_fail_flag, st, prof_events(ctx));
     else FIELD_CALL(ctx, launch_pedersen_rlc(a, d_fail_flag, st, prof_events(ctx)));
-  }
+    return VRFHIP_SUCCESS;
+  });
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return VRFHIP_SUCCESS;
 }
 
-int32_t rlc_host_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* input,
-                      const uint8_t* output, const uint8_t* pk_com, const uint8_t* r,
-                      const uint8_t* ok, const uint8_t* s, const uint8_t* sb,
-                      const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
-                      const uint8_t seed[32], uint8_t* status, int32_t* batch_ok) {
+int32_t rlc_host_impl(vrfhip_ctx* ctx, size_t n, bool affine, const PedIn& in, const Blob& ad, const uint8_t seed[32],
+                      uint8_t* status, int32_t* batch_ok) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (!seed) return fail(VRFHIP_ERR_BAD_ARG, "seed is NULL");
   if (batch_ok) *batch_ok = 1;
   if (n == 0) return VRFHIP_SUCCESS;
-  if (!input || !output || !pk_com || !r || !ok || !s || !sb || !status)
-    return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
-  if ((ad_len || ad_off) && !ad) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
-  size_t adb = blob_bytes(n, ad_off, ad_len, true);
+  if (in.any_null() || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  if (ad.missing()) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
+  StagedBlob s_ad(ad, n);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  const size_t pw = affine ? 64 : ctx->pt_bytes();
-  size_t need = 5 * Stage::pad(n * pw) + (affine ? 5 : 0) * Stage::pad(n * ctx->pt_bytes()) + 2 * Stage::pad(n * 32) +
-                Stage::pad(adb + 1) + Stage::pad((n + 1) * 4) + Stage::pad(n) + 256;
-  int32_t rc = ensure_stage(ctx, need);
+  const size_t pw = affine ? 64 : ctx->pt_bytes(), ew = ctx->pt_bytes();
+  PedStage d;
+  uint8_t *d_st, *d_flag, *d_enc[5];
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
+    d.take(sg, n, pw);
+    s_ad.take(sg);
+    d_st = sg.take(n);
+    d_flag = sg.take(1);
+    if (affine)                                  // the per-proof fallback wants compressed encodings
+      for (int i = 0; i < 5; ++i) d_enc[i] = sg.take(n * ew);
+  });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  const uint8_t* src[7] = {input, output, pk_com, r, ok, s, sb};
-  uint8_t* d[7];
-  for (int i = 0; i < 7; ++i) {
-    const size_t w = i < 5 ? pw : 32;
-    d[i] = sg.take(n * w);
-    HIP_TRY(hipMemcpyAsync(d[i], src[i], n * w, hipMemcpyHostToDevice, ctx->stream));
-  }
-  uint8_t* d_ad = sg.take(adb + 1);
-  uint32_t* d_off = reinterpret_cast<uint32_t*>(sg.take((n + 1) * 4));
-  uint8_t* d_st = sg.take(n);
-  uint8_t* d_flag = sg.take(1);
-  if (adb) HIP_TRY(hipMemcpyAsync(d_ad, ad, adb, hipMemcpyHostToDevice, ctx->stream));
-  if (ad_off) HIP_TRY(hipMemcpyAsync(d_off, ad_off, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  rc = rlc_dev_impl(ctx, n, affine, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d_ad,
-                    ad_off ? d_off : nullptr, ad_len, seed, d_st, d_flag, ctx->stream);
+  Blob d_ad;
+  if ((rc = d.send(ctx, in, n, pw)) || (rc = stage_blob(ctx, s_ad, &d_ad))) return rc;
+  rc = rlc_dev_impl(ctx, n, affine, d.dev(), d_ad, seed, d_st, d_flag, ctx->stream);
   if (rc) return rc;
   uint8_t flag = 0;
   HIP_TRY(hipMemcpyAsync(&flag, d_flag, 1, hipMemcpyDeviceToHost, ctx->stream));
@@ -1680,21 +1607,18 @@ int32_t rlc_host_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* inp
     // rejected as InvalidData keep that status (an off-curve affine point has no compressed form).
     if (batch_ok) *batch_ok = 0;
     if (affine) {
-      const size_t ew = ctx->pt_bytes();
       for (int i = 0; i < 5; ++i) {
-        uint8_t* enc = sg.take(n * ew);
         const int m256 = ctx->coords_mont256() ? 1 : 0;
-        if (ctx->sw) p256::launch_affine_compress(n, d[i], m256, enc, ctx->stream);
-        else if (ctx->bsw) launch_bsw_affine_compress(n, d[i], m256, enc, ctx->stream);
+        if (ctx->sw) p256::launch_affine_compress(n, d.d[i], m256, d_enc[i], ctx->stream);
+        else if (ctx->bsw) launch_bsw_affine_compress(n, d.d[i], m256, d_enc[i], ctx->stream);
         else {
-          if (m256) FIELD_CALL(ctx, launch_xy_from_mont256(n, d[i], ctx->stream));      // the staged copy, in place
-          FIELD_CALL(ctx, launch_affine_compress(n, d[i], enc, ctx->T.sq.str.flags, ctx->stream));
+          if (m256) FIELD_CALL(ctx, launch_xy_from_mont256(n, d.d[i], ctx->stream));      // the staged copy, in place
+          FIELD_CALL(ctx, launch_affine_compress(n, d.d[i], d_enc[i], ctx->T.sq.str.flags, ctx->stream));
         }
-        d[i] = enc;
+        d.d[i] = d_enc[i];
       }
     }
-    rc = vrfhip_pedersen_verify_batch_dev(ctx, n, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d_ad,
-                                          ad_off ? d_off : nullptr, ad_len, d_st, ctx->stream);
+    rc = ped_verify_dev_impl(ctx, n, false, d.dev(), d_ad, d_st, ctx->stream);
     if (rc) return rc;
     std::vector<uint8_t> item(n);
     HIP_TRY(hipMemcpyAsync(item.data(), d_st, n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1715,7 +1639,7 @@ int32_t vrfhip_pedersen_verify_batch_rlc_dev(vrfhip_ctx* ctx, size_t n, const ui
                                              const uint32_t* d_ad_off, uint32_t ad_len,
                                              const uint8_t seed[32], uint8_t* d_status,
                                              uint8_t* d_fail_flag, void* stream) {
-  return rlc_dev_impl(ctx, n, false, d_input, d_output, d_pk_com, d_r, d_ok, d_s, d_sb, d_ad, d_ad_off, ad_len,
+  return rlc_dev_impl(ctx, n, false, PedIn{d_input, d_output, d_pk_com, d_r, d_ok, d_s, d_sb}, Blob{d_ad, d_ad_off, ad_len, true},
                       seed, d_status, d_fail_flag, stream);
 }
 int32_t vrfhip_pedersen_verify_batch_rlc_affine_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_input_xy,
@@ -1725,15 +1649,15 @@ int32_t vrfhip_pedersen_verify_batch_rlc_affine_dev(vrfhip_ctx* ctx, size_t n, c
                                                     const uint8_t* d_ad, const uint32_t* d_ad_off,
                                                     uint32_t ad_len, const uint8_t seed[32],
                                                     uint8_t* d_status, uint8_t* d_fail_flag, void* stream) {
-  return rlc_dev_impl(ctx, n, true, d_input_xy, d_output_xy, d_pk_com_xy, d_r_xy, d_ok_xy, d_s, d_sb, d_ad,
-                      d_ad_off, ad_len, seed, d_status, d_fail_flag, stream);
+  return rlc_dev_impl(ctx, n, true, PedIn{d_input_xy, d_output_xy, d_pk_com_xy, d_r_xy, d_ok_xy, d_s, d_sb},
+                      Blob{d_ad, d_ad_off, ad_len, true}, seed, d_status, d_fail_flag, stream);
 }
 int32_t vrfhip_pedersen_verify_batch_rlc(vrfhip_ctx* ctx, size_t n, const uint8_t* input,
                                          const uint8_t* output, const uint8_t* pk_com, const uint8_t* r,
                                          const uint8_t* ok, const uint8_t* s, const uint8_t* sb,
                                          const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
                                          const uint8_t seed[32], uint8_t* status, int32_t* batch_ok) {
-  return rlc_host_impl(ctx, n, false, input, output, pk_com, r, ok, s, sb, ad, ad_off, ad_len, seed, status,
+  return rlc_host_impl(ctx, n, false, PedIn{input, output, pk_com, r, ok, s, sb}, Blob{ad, ad_off, ad_len, true}, seed, status,
                        batch_ok);
 }
 int32_t vrfhip_pedersen_verify_batch_rlc_affine(vrfhip_ctx* ctx, size_t n, const uint8_t* input_xy,
@@ -1742,7 +1666,7 @@ int32_t vrfhip_pedersen_verify_batch_rlc_affine(vrfhip_ctx* ctx, size_t n, const
                                                 const uint8_t* sb, const uint8_t* ad, const uint32_t* ad_off,
                                                 uint32_t ad_len, const uint8_t seed[32], uint8_t* status,
                                                 int32_t* batch_ok) {
-  return rlc_host_impl(ctx, n, true, input_xy, output_xy, pk_com_xy, r_xy, ok_xy, s, sb, ad, ad_off, ad_len,
+  return rlc_host_impl(ctx, n, true, PedIn{input_xy, output_xy, pk_com_xy, r_xy, ok_xy, s, sb}, Blob{ad, ad_off, ad_len, true},
                        seed, status, batch_ok);
 }
 
@@ -1820,14 +1744,15 @@ int32_t vrfhip_msm(vrfhip_ctx* ctx, size_t n, const uint8_t* bases_xy, const uin
   if (n && (!bases_xy || !scalars)) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  int32_t rc = ensure_stage(ctx, Stage::pad(n * 64 + 1) + Stage::pad(n * 32 + 1) + 3 * 256);
+  uint8_t *d_xy, *d_k, *d_out, *d_oxy, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
+    d_xy = sg.take(n * 64 + 1);
+    d_k = sg.take(n * 32 + 1);
+    d_out = sg.take(64);                    // 32 (Edwards) or 33 (Sec1) bytes are used
+    d_oxy = sg.take(64);
+    d_st = sg.take(1);
+  });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t* d_xy = sg.take(n * 64 + 1);
-  uint8_t* d_k = sg.take(n * 32 + 1);
-  uint8_t* d_out = sg.take(64);             // 32 (Edwards) or 33 (Sec1) bytes are used
-  uint8_t* d_oxy = sg.take(64);
-  uint8_t* d_st = sg.take(1);
   if (n) {
     HIP_TRY(hipMemcpyAsync(d_xy, bases_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_k, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
@@ -1846,7 +1771,7 @@ int32_t vrfhip_pairing_check_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t*
                                        const uint8_t* d_g2, int32_t g2_shared, uint8_t* d_status,
                                        void* stream) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (n == 0) return VRFHIP_SUCCESS;
   if (!d_g1 || !d_g2 || !d_status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
@@ -1875,18 +1800,15 @@ int32_t vrfhip_pairing_check_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t*
 int32_t vrfhip_pairing_check_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2,
                                    int32_t g2_shared, uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (n == 0) return VRFHIP_SUCCESS;
   if (!g1 || !g2 || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
   size_t g2b = g2_shared ? 384 : n * 384;
-  int32_t rc = ensure_stage(ctx, Stage::pad(n * 192) + Stage::pad(g2b) + Stage::pad(n));
+  uint8_t *d_g1, *d_g2, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) { d_g1 = sg.take(n * 192); d_g2 = sg.take(g2b); d_st = sg.take(n); });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t* d_g1 = sg.take(n * 192);
-  uint8_t* d_g2 = sg.take(g2b);
-  uint8_t* d_st = sg.take(n);
   HIP_TRY(hipMemcpyAsync(d_g1, g1, n * 192, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(d_g2, g2, g2b, hipMemcpyHostToDevice, ctx->stream));
   rc = vrfhip_pairing_check_batch_dev(ctx, n, d_g1, d_g2, g2_shared, d_st, ctx->stream);
@@ -1900,7 +1822,7 @@ int32_t vrfhip_pairing_check_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* g1,
 int32_t vrfhip_g1_msm_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_bases, const uint8_t* d_scalars, uint8_t* d_out,
                           uint8_t* d_status, void* stream) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (!d_out || !d_status) return fail(VRFHIP_ERR_BAD_ARG, "NULL output");
   if (n && (!d_bases || !d_scalars)) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   if (n > (size_t(1) << 28)) return fail(VRFHIP_ERR_BAD_ARG, "batch too large");
@@ -1920,18 +1842,19 @@ int32_t vrfhip_g1_msm_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_bases, con
 int32_t vrfhip_g1_msm(vrfhip_ctx* ctx, size_t n, const uint8_t* bases, const uint8_t* scalars, uint8_t* out,
                       uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (!out || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL output");
   if (n && (!bases || !scalars)) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  int32_t rc = ensure_stage(ctx, Stage::pad(n * 96 + 1) + Stage::pad(n * 32 + 1) + 2 * 256);
+  uint8_t *d_b, *d_k, *d_o, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
+    d_b = sg.take(n * 96 + 1);
+    d_k = sg.take(n * 32 + 1);
+    d_o = sg.take(96);
+    d_st = sg.take(1);
+  });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t* d_b = sg.take(n * 96 + 1);
-  uint8_t* d_k = sg.take(n * 32 + 1);
-  uint8_t* d_o = sg.take(96);
-  uint8_t* d_st = sg.take(1);
   if (n) {
     HIP_TRY(hipMemcpyAsync(d_b, bases, n * 96, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_k, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
@@ -1948,7 +1871,7 @@ int32_t vrfhip_g1_msm(vrfhip_ctx* ctx, size_t n, const uint8_t* bases, const uin
 int32_t vrfhip_pairing_check_batch_rlc_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_g1, const uint8_t* d_g2_shared,
                                            const uint8_t seed[32], uint8_t* d_status, uint8_t* d_verdict, void* stream) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (!d_verdict || !seed) return fail(VRFHIP_ERR_BAD_ARG, "NULL verdict or seed");
   if (n && (!d_g1 || !d_g2_shared || !d_status)) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   if (n > (size_t(1) << 28)) return fail(VRFHIP_ERR_BAD_ARG, "batch too large");
@@ -1970,7 +1893,7 @@ int32_t vrfhip_pairing_check_batch_rlc_dev(vrfhip_ctx* ctx, size_t n, const uint
   ds.p[0] = d_g1; ds.w[0] = 192; ds.n_arr = 1;
   // ... and on the shared G2 pair, absorbed as the leaves' common byte string (with the pair outside the digest a
   // caller-influenced pair could be chosen after the weights, Q1 = a Q0 with a = -(sum z alpha) / (sum z beta))
-  ds.ad = make_view(d_g2_shared, nullptr, 384, true);
+  ds.ad = Blob{d_g2_shared, nullptr, 384, true}.view(0);
   launch_batch_digest(ds, n, 0, d_digest_ws, d_root, st);   // the weights depend on every byte of the batch
   launch_g1_rlc(L, d_g1, seed, d_root, 0, d_status, st, ev ? ev + 1 : nullptr);
   // one pairing check for the whole batch: (sum z A, sum z B) against the shared pair (prepared lines)
@@ -1983,20 +1906,21 @@ int32_t vrfhip_pairing_check_batch_rlc_dev(vrfhip_ctx* ctx, size_t n, const uint
 int32_t vrfhip_pairing_check_batch_rlc(vrfhip_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2_shared,
                                        const uint8_t seed[32], uint8_t* status, int32_t* batch_ok) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (!seed) return fail(VRFHIP_ERR_BAD_ARG, "seed is NULL");
   if (batch_ok) *batch_ok = 1;
   if (n == 0) return VRFHIP_SUCCESS;
   if (!g1 || !g2_shared || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  int32_t rc = ensure_stage(ctx, Stage::pad(n * 192) + Stage::pad(384) + Stage::pad(n) + 256);
+  uint8_t *d_g1, *d_g2, *d_st, *d_v;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
+    d_g1 = sg.take(n * 192);
+    d_g2 = sg.take(384);
+    d_st = sg.take(n);
+    d_v = sg.take(1);
+  });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t* d_g1 = sg.take(n * 192);
-  uint8_t* d_g2 = sg.take(384);
-  uint8_t* d_st = sg.take(n);
-  uint8_t* d_v = sg.take(1);
   HIP_TRY(hipMemcpyAsync(d_g1, g1, n * 192, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(d_g2, g2_shared, 384, hipMemcpyHostToDevice, ctx->stream));
   rc = vrfhip_pairing_check_batch_rlc_dev(ctx, n, d_g1, d_g2, seed, d_st, d_v, ctx->stream);
@@ -2018,16 +1942,14 @@ int32_t vrfhip_pairing_check_batch_rlc(vrfhip_ctx* ctx, size_t n, const uint8_t*
 // Test-only: quad-distributed Fp12 tower operations against the one-lane operations (k_pairing.hip)
 int32_t vrfhip_test_pairing_quad_ops(vrfhip_ctx* ctx, size_t n, const uint8_t* fp12_pairs, uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (n == 0) return VRFHIP_SUCCESS;
   if (!fp12_pairs || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  int32_t rc = ensure_stage(ctx, Stage::pad(n * 1152) + Stage::pad(n));
+  uint8_t *d_in, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) { d_in = sg.take(n * 1152); d_st = sg.take(n); });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t* d_in = sg.take(n * 1152);
-  uint8_t* d_st = sg.take(n);
   HIP_TRY(hipMemcpyAsync(d_in, fp12_pairs, n * 1152, hipMemcpyHostToDevice, ctx->stream));
   launch_pairing_quad_selftest(n, d_in, d_st, ctx->stream);
   launch_pairing_row_selftest(n, d_in, d_st, ctx->stream);        // bits 64 / 128: the row-distributed tower
@@ -2040,16 +1962,14 @@ int32_t vrfhip_test_pairing_quad_ops(vrfhip_ctx* ctx, size_t n, const uint8_t* f
 // Test-only: the 8-lanes-per-item Fp12 tower (bls12_oct.cuh) and its cross-lane moves against the one-lane operations
 int32_t vrfhip_test_pairing_oct_ops(vrfhip_ctx* ctx, size_t n, const uint8_t* fp12_pairs, uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (n == 0) return VRFHIP_SUCCESS;
   if (!fp12_pairs || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  int32_t rc = ensure_stage(ctx, Stage::pad(n * 1152) + Stage::pad(n));
+  uint8_t *d_in, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) { d_in = sg.take(n * 1152); d_st = sg.take(n); });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t* d_in = sg.take(n * 1152);
-  uint8_t* d_st = sg.take(n);
   HIP_TRY(hipMemcpyAsync(d_in, fp12_pairs, n * 1152, hipMemcpyHostToDevice, ctx->stream));
   launch_pairing_oct_selftest(n, d_in, d_st, ctx->stream);
   HIP_TRY(hipGetLastError());
@@ -2062,75 +1982,56 @@ int32_t vrfhip_test_pairing_oct_ops(vrfhip_ctx* ctx, size_t n, const uint8_t* fp
 int32_t vrfhip_hash_to_curve_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_msg,
                                        const uint32_t* d_msg_off, uint32_t msg_len,
                                        uint8_t* d_points, void* stream) {
+  const Blob msg{d_msg, d_msg_off, msg_len, false};
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
-  if (!d_points || (!d_msg && (msg_len || d_msg_off))) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  if (!d_points || msg.missing()) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!ctx->sw && !ctx->bsw && ctx->suite == VRFHIP_SUITE_BANDERSNATCH_SHA512_ELL2) {      // Elligator 2: one launch, no counters
+    FIELD_CALL(ctx, launch_hash_to_curve((int)ctx->suite, n, msg.view(0), d_points, ctx->T, st));
+    HIP_TRY(hipGetLastError());
+    return VRFHIP_SUCCESS;
+  }
   // The try-and-increment suites find their counters with the provers' work-queue search, which wants one byte per item: a
   // buffer of its own (n bytes, at most 2^20 per chunk) -- not the prove / verify workspace (7 KiB per item), which this
   // entry point neither needs nor should resize.
   const size_t chunk = std::min<size_t>(n, size_t(1) << 20);
-  if (ctx->sw || ctx->bsw || ctx->suite != VRFHIP_SUITE_BANDERSNATCH_SHA512_ELL2) {
-    if (ctx->h2c_cap < chunk) {
-      if (ctx->d_h2c_ctr) { (void)hipStreamSynchronize(static_cast<hipStream_t>(stream)); (void)hipFree(ctx->d_h2c_ctr); ctx->d_h2c_ctr = nullptr; ctx->h2c_cap = 0; }
-      if (hipMalloc(&ctx->d_h2c_ctr, chunk) != hipSuccess) return fail(VRFHIP_ERR_OOM, "hipMalloc(hash-to-curve counters) failed");
-      ctx->h2c_cap = chunk;
-    }
+  if (ctx->h2c_cap < chunk) {
+    if (ctx->d_h2c_ctr) { (void)hipStreamSynchronize(st); (void)hipFree(ctx->d_h2c_ctr); ctx->d_h2c_ctr = nullptr; ctx->h2c_cap = 0; }
+    if (hipMalloc(&ctx->d_h2c_ctr, chunk) != hipSuccess) return fail(VRFHIP_ERR_OOM, "hipMalloc(hash-to-curve counters) failed");
+    ctx->h2c_cap = chunk;
   }
-  if (ctx->sw) {
-    for (size_t base = 0; base < n; base += chunk) {
-      const size_t m = std::min(chunk, n - base);
-      BytesView mv = d_msg_off ? make_view(d_msg, d_msg_off + base, msg_len, false)
-                               : make_view(d_msg ? d_msg + base * (size_t)msg_len : d_msg, nullptr, msg_len, false);
-      p256::launch_hash_to_curve(m, mv, d_points + base * 33, ctx->T.sq.str, static_cast<hipStream_t>(stream), ctx->d_h2c_ctr,
-                                 ctx->d_queue);
-    }
-  } else if (ctx->bsw) {
-    for (size_t base = 0; base < n; base += chunk) {
-      const size_t m = std::min(chunk, n - base);
-      BytesView mv = d_msg_off ? make_view(d_msg, d_msg_off + base, msg_len, false)
-                               : make_view(d_msg ? d_msg + base * (size_t)msg_len : d_msg, nullptr, msg_len, false);
-      launch_bsw_hash_to_curve(m, mv, d_points + base * 33, ctx->T, static_cast<hipStream_t>(stream), ctx->d_h2c_ctr, ctx->d_queue);
-    }
-  } else if (ctx->suite == VRFHIP_SUITE_BANDERSNATCH_SHA512_ELL2) {
-    FIELD_CALL(ctx, launch_hash_to_curve((int)ctx->suite, n, make_view(d_msg, d_msg_off, msg_len, false), d_points, ctx->T,
-                                         static_cast<hipStream_t>(stream)));
-  } else {
-    for (size_t base = 0; base < n; base += chunk) {
-      const size_t m = std::min(chunk, n - base);
-      BytesView mv = d_msg_off ? make_view(d_msg, d_msg_off + base, msg_len, false)
-                               : make_view(d_msg ? d_msg + base * (size_t)msg_len : d_msg, nullptr, msg_len, false);
-      FIELD_CALL(ctx, launch_hash_to_curve((int)ctx->suite, m, mv, d_points + base * 32, ctx->T, static_cast<hipStream_t>(stream),
-                                           ctx->d_h2c_ctr, ctx->d_queue));
-    }
-  }
+  const size_t pw = ctx->pt_bytes();
+  for_chunks(n, chunk, [&](size_t base, size_t m) -> int32_t {
+    const BytesView mv = msg.view(base);
+    uint8_t* out = d_points + base * pw;
+    if (ctx->sw) p256::launch_hash_to_curve(m, mv, out, ctx->T.sq.str, st, ctx->d_h2c_ctr, ctx->d_queue);
+    else if (ctx->bsw) launch_bsw_hash_to_curve(m, mv, out, ctx->T, st, ctx->d_h2c_ctr, ctx->d_queue);
+    else FIELD_CALL(ctx, launch_hash_to_curve((int)ctx->suite, m, mv, out, ctx->T, st, ctx->d_h2c_ctr, ctx->d_queue));
+    return VRFHIP_SUCCESS;
+  });
   HIP_TRY(hipGetLastError());
   return VRFHIP_SUCCESS;
 }
 
 int32_t vrfhip_hash_to_curve_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* msg,
                                    const uint32_t* msg_off, uint32_t msg_len, uint8_t* points) {
+  const Blob h_msg{msg, msg_off, msg_len, false};
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
-  if (!points || (!msg && (msg_len || msg_off))) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
-  size_t msgb = blob_bytes(n, msg_off, msg_len, false);
-  uint8_t *d_msg, *d_pts;
-  uint32_t* d_off;
+  if (!points || h_msg.missing()) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  StagedBlob s_msg(h_msg, n);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  {
-    int32_t rc = ensure_stage(ctx, Stage::pad(msgb + 1) + Stage::pad((n + 1) * 4) + Stage::pad(n * ctx->pt_bytes()));
-    if (rc) return rc;
-    Stage sg(ctx->d_stage);
-    d_msg = sg.take(msgb + 1);
-    d_off = reinterpret_cast<uint32_t*>(sg.take((n + 1) * 4));
-    d_pts = sg.take(n * ctx->pt_bytes());
-    if (msgb) HIP_TRY(hipMemcpyAsync(d_msg, msg, msgb, hipMemcpyHostToDevice, ctx->stream));
-    if (msg_off) HIP_TRY(hipMemcpyAsync(d_off, msg_off, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  }
-  int32_t rc = vrfhip_hash_to_curve_batch_dev(ctx, n, d_msg, msg_off ? d_off : nullptr, msg_len, d_pts,
-                                              ctx->stream);
+  uint8_t* d_pts;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) { s_msg.take(sg); d_pts = sg.take(n * ctx->pt_bytes()); });
+  if (rc) return rc;
+  Blob d_msg;
+  rc = stage_blob(ctx, s_msg, &d_msg);
+  if (rc) return rc;
+  rc = vrfhip_hash_to_curve_batch_dev(ctx, n, d_msg.p, d_msg.off, msg_len, d_pts, ctx->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(points, d_pts, n * ctx->pt_bytes(), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -2159,15 +2060,10 @@ int32_t vrfhip_output_hash_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* outpu
   uint8_t *d_in, *d_out;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  {
-    int32_t rc = ensure_stage(ctx, Stage::pad(n * ctx->pt_bytes()) + Stage::pad(n * 64));
-    if (rc) return rc;
-    Stage sg(ctx->d_stage);
-    d_in = sg.take(n * ctx->pt_bytes());
-    d_out = sg.take(n * 64);
-    HIP_TRY(hipMemcpyAsync(d_in, output, n * ctx->pt_bytes(), hipMemcpyHostToDevice, ctx->stream));
-  }
-  int32_t rc = vrfhip_output_hash_batch_dev(ctx, n, d_in, d_out, ctx->stream);
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) { d_in = sg.take(n * ctx->pt_bytes()); d_out = sg.take(n * 64); });
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(d_in, output, n * ctx->pt_bytes(), hipMemcpyHostToDevice, ctx->stream));
+  rc = vrfhip_output_hash_batch_dev(ctx, n, d_in, d_out, ctx->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(hash, d_out, n * ctx->hash_bytes(), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -2199,17 +2095,14 @@ int32_t vrfhip_secret_from_seed_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* 
   uint8_t *d_seed, *d_sk, *d_pk;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  {
-    int32_t rc = ensure_stage(ctx, Stage::pad(n * (size_t)seed_len + 1) + Stage::pad(n * 32) + Stage::pad(n * ctx->pt_bytes()));
-    if (rc) return rc;
-    Stage sg(ctx->d_stage);
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
     d_seed = sg.take(n * (size_t)seed_len + 1);
     d_sk = sg.take(n * 32);
     d_pk = sg.take(n * ctx->pt_bytes());
-    if (seed_len)
-      HIP_TRY(hipMemcpyAsync(d_seed, seeds, n * (size_t)seed_len, hipMemcpyHostToDevice, ctx->stream));
-  }
-  int32_t rc = vrfhip_secret_from_seed_batch_dev(ctx, n, d_seed, seed_len, d_sk, pk_out ? d_pk : nullptr,
+  });
+  if (rc) return rc;
+  if (seed_len) HIP_TRY(hipMemcpyAsync(d_seed, seeds, n * (size_t)seed_len, hipMemcpyHostToDevice, ctx->stream));
+  rc = vrfhip_secret_from_seed_batch_dev(ctx, n, d_seed, seed_len, d_sk, pk_out ? d_pk : nullptr,
                                                  ctx->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(sk_out, d_sk, n * 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -2241,13 +2134,13 @@ int32_t vrfhip_point_validate_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t
   int32_t rc = ensure_workspace(ctx, n);
   if (rc) return rc;
   // one window table per item: the tabs region holds WS_TABS per workspace item
-  size_t cap = ctx->ws_cap * WS_TABS;
-  for (size_t base = 0; base < n; base += cap) {
-    size_t m = std::min(cap, n - base);
-    FIELD_CALL(ctx, launch_point_validate((int)ctx->suite, m, d_points + base * 32, d_xy_out ? d_xy_out + base * 64 : nullptr,
-                          d_status + base, ctx->ws.tabs, ctx->T, static_cast<hipStream_t>(stream)));
-    if (d_xy_out && ctx->coords_mont256()) FIELD_CALL(ctx, launch_xy_to_mont256(m, d_xy_out + base * 64, static_cast<hipStream_t>(stream)));
-  }
+  for_chunks(n, ctx->ws_cap * WS_TABS, [&](size_t base, size_t m) -> int32_t {
+    uint8_t* xy = at(d_xy_out, base, 64);
+    FIELD_CALL(ctx, launch_point_validate((int)ctx->suite, m, d_points + base * 32, xy, d_status + base, ctx->ws.tabs, ctx->T,
+                                          static_cast<hipStream_t>(stream)));
+    if (xy && ctx->coords_mont256()) FIELD_CALL(ctx, launch_xy_to_mont256(m, xy, static_cast<hipStream_t>(stream)));
+    return VRFHIP_SUCCESS;
+  });
   HIP_TRY(hipGetLastError());
   return VRFHIP_SUCCESS;
 }
@@ -2260,16 +2153,14 @@ int32_t vrfhip_point_validate_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* po
   uint8_t *d_in, *d_xy, *d_st;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  {
-    int32_t rc = ensure_stage(ctx, Stage::pad(n * ctx->pt_bytes()) + Stage::pad(n * 64) + Stage::pad(n));
-    if (rc) return rc;
-    Stage sg(ctx->d_stage);
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
     d_in = sg.take(n * ctx->pt_bytes());
     d_xy = sg.take(n * 64);
     d_st = sg.take(n);
-    HIP_TRY(hipMemcpyAsync(d_in, points, n * ctx->pt_bytes(), hipMemcpyHostToDevice, ctx->stream));
-  }
-  int32_t rc = vrfhip_point_validate_batch_dev(ctx, n, d_in, xy_out ? d_xy : nullptr, d_st, ctx->stream);
+  });
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(d_in, points, n * ctx->pt_bytes(), hipMemcpyHostToDevice, ctx->stream));
+  rc = vrfhip_point_validate_batch_dev(ctx, n, d_in, xy_out ? d_xy : nullptr, d_st, ctx->stream);
   if (rc) return rc;
   if (xy_out) HIP_TRY(hipMemcpyAsync(xy_out, d_xy, n * 64, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
@@ -2301,12 +2192,9 @@ int32_t vrfhip_te_sw_map_batch(vrfhip_ctx* ctx, size_t n, int32_t to_te, const u
   if (!in_xy || !out_xy || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  int32_t rc = ensure_stage(ctx, 2 * Stage::pad(n * 64) + Stage::pad(n));
+  uint8_t *d_in, *d_out, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) { d_in = sg.take(n * 64); d_out = sg.take(n * 64); d_st = sg.take(n); });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t* d_in = sg.take(n * 64);
-  uint8_t* d_out = sg.take(n * 64);
-  uint8_t* d_st = sg.take(n);
   HIP_TRY(hipMemcpyAsync(d_in, in_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
   rc = vrfhip_te_sw_map_batch_dev(ctx, n, to_te, d_in, d_out, d_st, ctx->stream);
   if (rc) return rc;
@@ -2319,17 +2207,14 @@ int32_t vrfhip_te_sw_map_batch(vrfhip_ctx* ctx, size_t n, int32_t to_te, const u
 int32_t vrfhip_fq_mul_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* a, const uint8_t* b,
                             uint8_t* r) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (n == 0) return VRFHIP_SUCCESS;
   if (!a || !b || !r) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  int32_t rc = ensure_stage(ctx, 3 * Stage::pad(n * 32));
+  uint8_t *d_a, *d_b, *d_r;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) { d_a = sg.take(n * 32); d_b = sg.take(n * 32); d_r = sg.take(n * 32); });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t* d_a = sg.take(n * 32);
-  uint8_t* d_b = sg.take(n * 32);
-  uint8_t* d_r = sg.take(n * 32);
   HIP_TRY(hipMemcpyAsync(d_a, a, n * 32, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(d_b, b, n * 32, hipMemcpyHostToDevice, ctx->stream));
   FIELD_CALL(ctx, launch_fq_mul(n, d_a, d_b, d_r, ctx->stream));
@@ -2344,16 +2229,15 @@ int32_t vrfhip_fq_mul_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* a, const u
 int32_t vrfhip_test_point_add(vrfhip_ctx* ctx, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out,
                               uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (ctx->bsw) return fail(VRFHIP_ERR_UNSUPPORTED, BSW_UNSUPPORTED_MSG);
   if (n == 0) return VRFHIP_SUCCESS;
   if (!a || !b || !out || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  int32_t rc = ensure_stage(ctx, 3 * Stage::pad(n * 32) + Stage::pad(n));
+  uint8_t *d_a, *d_b, *d_o, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) { d_a = sg.take(n * 32); d_b = sg.take(n * 32); d_o = sg.take(n * 32); d_st = sg.take(n); });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t *d_a = sg.take(n * 32), *d_b = sg.take(n * 32), *d_o = sg.take(n * 32), *d_st = sg.take(n);
   HIP_TRY(hipMemcpyAsync(d_a, a, n * 32, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(d_b, b, n * 32, hipMemcpyHostToDevice, ctx->stream));
   FIELD_CALL(ctx, launch_test_point_add((int)ctx->suite, n, d_a, d_b, d_o, d_st, ctx->T, ctx->stream));
@@ -2367,7 +2251,7 @@ int32_t vrfhip_test_point_add(vrfhip_ctx* ctx, size_t n, const uint8_t* a, const
 int32_t vrfhip_test_scalar_mul(vrfhip_ctx* ctx, size_t n, const uint8_t* scalars, const uint8_t* points, uint8_t* out,
                                uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (ctx->bsw) return fail(VRFHIP_ERR_UNSUPPORTED, BSW_UNSUPPORTED_MSG);
   if (n == 0) return VRFHIP_SUCCESS;
   if (!scalars || !points || !out || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
@@ -2375,18 +2259,16 @@ int32_t vrfhip_test_scalar_mul(vrfhip_ctx* ctx, size_t n, const uint8_t* scalars
   DeviceGuard guard(ctx->device);
   int32_t rc = ensure_workspace(ctx, n);
   if (rc) return rc;
-  rc = ensure_stage(ctx, 3 * Stage::pad(n * 32) + Stage::pad(n));
+  uint8_t *d_k, *d_p, *d_o, *d_st;
+  rc = stage_layout(ctx, [&](Stage& sg) { d_k = sg.take(n * 32); d_p = sg.take(n * 32); d_o = sg.take(n * 32); d_st = sg.take(n); });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t *d_k = sg.take(n * 32), *d_p = sg.take(n * 32), *d_o = sg.take(n * 32), *d_st = sg.take(n);
   HIP_TRY(hipMemcpyAsync(d_k, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(d_p, points, n * 32, hipMemcpyHostToDevice, ctx->stream));
-  const size_t cap = ctx->ws_cap * (WS_TABS / 2);          // two window tables per item
-  for (size_t base = 0; base < n; base += cap) {
-    size_t m = std::min(cap, n - base);
+  for_chunks(n, ctx->ws_cap * (WS_TABS / 2), [&](size_t base, size_t m) -> int32_t {      // two window tables per item
     FIELD_CALL(ctx, launch_test_scalar_mul((int)ctx->suite, m, d_k + base * 32, d_p + base * 32, d_o + base * 32, d_st + base,
                            ctx->ws.tabs, ctx->T, ctx->stream));
-  }
+    return VRFHIP_SUCCESS;
+  });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, d_o, n * 32, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
@@ -2399,24 +2281,21 @@ namespace {
 int32_t test_hash_impl(vrfhip_ctx* ctx, size_t n, const uint8_t* msg, const uint32_t* msg_off, uint32_t msg_len,
                        uint8_t* out, int which) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (ctx->bsw) return fail(VRFHIP_ERR_UNSUPPORTED, BSW_UNSUPPORTED_MSG);
   if (n == 0) return VRFHIP_SUCCESS;
   if (!out || (!msg && (msg_len || msg_off))) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
   const size_t ob = which ? 96 : 64;
-  size_t msgb = blob_bytes(n, msg_off, msg_len, false);
+  StagedBlob s_msg(Blob{msg, msg_off, msg_len, false}, n);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  int32_t rc = ensure_stage(ctx, Stage::pad(msgb + 1) + Stage::pad((n + 1) * 4) + Stage::pad(n * ob));
+  uint8_t* d_out;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) { s_msg.take(sg); d_out = sg.take(n * ob); });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
-  uint8_t* d_msg = sg.take(msgb + 1);
-  uint32_t* d_off = reinterpret_cast<uint32_t*>(sg.take((n + 1) * 4));
-  uint8_t* d_out = sg.take(n * ob);
-  if (msgb) HIP_TRY(hipMemcpyAsync(d_msg, msg, msgb, hipMemcpyHostToDevice, ctx->stream));
-  if (msg_off) HIP_TRY(hipMemcpyAsync(d_off, msg_off, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  FIELD_CALL(ctx, launch_test_hash((int)ctx->suite, n, make_view(d_msg, msg_off ? d_off : nullptr, msg_len, false), d_out, which, ctx->T,
-                   ctx->stream));
+  Blob d_msg;
+  rc = stage_blob(ctx, s_msg, &d_msg);
+  if (rc) return rc;
+  FIELD_CALL(ctx, launch_test_hash((int)ctx->suite, n, d_msg.view(0), d_out, which, ctx->T, ctx->stream));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, d_out, n * ob, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -2470,9 +2349,6 @@ struct BlobSlice {
     }
   }
 };
-const uint8_t* at32(const uint8_t* p, size_t i) { return p ? p + i * 32 : nullptr; }
-uint8_t* at32(uint8_t* p, size_t i) { return p ? p + i * 32 : nullptr; }
-uint8_t* at_w(uint8_t* p, size_t i, size_t w) { return p ? p + i * w : nullptr; }
 // width of a compressed point on the wire for a set of contexts (32; 33 for secp256r1): all must agree
 size_t point_bytes_of(vrfhip_ctx* const* ctxs, int32_t n_ctx) {
   if (!ctxs || n_ctx < 1 || !ctxs[0]) return 32;              // run_sharded reports the bad argument
@@ -2520,36 +2396,34 @@ int32_t vrfhip_test_batch_digest(vrfhip_ctx* ctx, size_t n, int32_t n_arr, const
                                  const uint32_t* widths, const uint8_t* ad, const uint32_t* ad_off, uint32_t ad_len,
                                  uint64_t index0, uint8_t root[32]) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
-  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, "not available for the secp256r1 suite (the IETF and Pedersen schemes per proof, hash-to-curve, output hash, keys and point validation are)");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
   if (!root || !arrays || !widths || n == 0) return fail(VRFHIP_ERR_BAD_ARG, "NULL argument or empty batch");
   if (n_arr < 1 || n_arr > DIGEST_MAX_ARRAYS) return fail(VRFHIP_ERR_BAD_ARG, "1..8 arrays");
   if ((ad_len || ad_off) && !ad) return fail(VRFHIP_ERR_BAD_ARG, "ad is NULL");
-  size_t need = Stage::pad(digest_ws_bytes(n)) + 512, adb = blob_bytes(n, ad_off, ad_len, true);
-  for (int32_t j = 0; j < n_arr; ++j) {
+  for (int32_t j = 0; j < n_arr; ++j)
     if (!arrays[j] || widths[j] == 0 || widths[j] % 4) return fail(VRFHIP_ERR_BAD_ARG, "array NULL or width not a multiple of 4");
-    need += Stage::pad(n * (size_t)widths[j]);
-  }
-  need += Stage::pad(adb + 1) + Stage::pad((n + 1) * 4);
+  StagedBlob s_ad(Blob{ad, ad_off, ad_len, true}, n);
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   DeviceGuard guard(ctx->device);
-  int32_t rc = ensure_stage(ctx, need);
+  uint8_t *d_arr[DIGEST_MAX_ARRAYS], *d_ws, *d_root;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
+    for (int32_t j = 0; j < n_arr; ++j) d_arr[j] = sg.take(n * (size_t)widths[j]);
+    s_ad.take(sg);
+    d_ws = sg.take(digest_ws_bytes(n));
+    d_root = sg.take(32);
+  });
   if (rc) return rc;
-  Stage sg(ctx->d_stage);
   DigestSrc ds{};
   ds.n_arr = n_arr;
   for (int32_t j = 0; j < n_arr; ++j) {
-    uint8_t* d = sg.take(n * (size_t)widths[j]);
-    HIP_TRY(hipMemcpyAsync(d, arrays[j], n * (size_t)widths[j], hipMemcpyHostToDevice, ctx->stream));
-    ds.p[j] = d;
+    HIP_TRY(hipMemcpyAsync(d_arr[j], arrays[j], n * (size_t)widths[j], hipMemcpyHostToDevice, ctx->stream));
+    ds.p[j] = d_arr[j];
     ds.w[j] = widths[j];
   }
-  uint8_t* d_ad = sg.take(adb + 1);
-  uint32_t* d_off = reinterpret_cast<uint32_t*>(sg.take((n + 1) * 4));
-  if (adb) HIP_TRY(hipMemcpyAsync(d_ad, ad, adb, hipMemcpyHostToDevice, ctx->stream));
-  if (ad_off) HIP_TRY(hipMemcpyAsync(d_off, ad_off, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (ad) ds.ad = make_view(d_ad, ad_off ? d_off : nullptr, ad_len, true);
-  uint8_t* d_ws = sg.take(digest_ws_bytes(n));
-  uint8_t* d_root = sg.take(32);
+  Blob d_ad;
+  rc = stage_blob(ctx, s_ad, &d_ad);
+  if (rc) return rc;
+  if (ad) ds.ad = d_ad.view(0);
   launch_batch_digest(ds, n, index0, d_ws, d_root, ctx->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(root, d_root, 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -2566,7 +2440,7 @@ int32_t vrfhip_ietf_verify_batch_multi(vrfhip_ctx* const* ctxs, int32_t n_ctx, s
   if (!pw) return fail(VRFHIP_ERR_BAD_ARG, "contexts disagree on the suite's point encoding");
   return run_sharded(ctxs, n_ctx, n, [&](vrfhip_ctx* ctx, size_t lo, size_t hi) {
     BlobSlice a(ad, ad_off, ad_len, true, lo, hi);
-    return vrfhip_ietf_verify_batch(ctx, hi - lo, pk + lo * pw, input + lo * pw, output + lo * pw, at32(c, lo), at32(s, lo),
+    return vrfhip_ietf_verify_batch(ctx, hi - lo, pk + lo * pw, input + lo * pw, output + lo * pw, at(c, lo, 32), at(s, lo, 32),
                                     a.blob, a.off, ad_len, status + lo);
   });
 }
@@ -2581,9 +2455,9 @@ int32_t vrfhip_ietf_prove_batch_multi(vrfhip_ctx* const* ctxs, int32_t n_ctx, si
   if (!w || !pw) return fail(VRFHIP_ERR_BAD_ARG, "contexts disagree on VRFHIP_FLAG_PROVE_POINTS_AFFINE or on the suite's point encoding");
   return run_sharded(ctxs, n_ctx, n, [&](vrfhip_ctx* ctx, size_t lo, size_t hi) {
     BlobSlice m(msg, input ? nullptr : msg_off, msg_len, false, lo, hi), a(ad, ad_off, ad_len, true, lo, hi);
-    return vrfhip_ietf_prove_batch(ctx, hi - lo, at32(sk, lo), m.blob, m.off, msg_len, input ? input + lo * pw : nullptr, a.blob, a.off,
-                                   ad_len, at_w(output, lo, w), at32(c, lo), at32(s, lo), at_w(pk_out, lo, w),
-                                   at_w(input_out, lo, pw), status ? status + lo : nullptr);
+    return vrfhip_ietf_prove_batch(ctx, hi - lo, at(sk, lo, 32), m.blob, m.off, msg_len, input ? input + lo * pw : nullptr, a.blob, a.off,
+                                   ad_len, at(output, lo, w), at(c, lo, 32), at(s, lo, 32), at(pk_out, lo, w),
+                                   at(input_out, lo, pw), status ? status + lo : nullptr);
   });
 }
 
@@ -2598,9 +2472,9 @@ int32_t vrfhip_pedersen_prove_batch_multi(vrfhip_ctx* const* ctxs, int32_t n_ctx
   if (!w || !pw) return fail(VRFHIP_ERR_BAD_ARG, "contexts disagree on VRFHIP_FLAG_PROVE_POINTS_AFFINE or on the suite's point encoding");
   return run_sharded(ctxs, n_ctx, n, [&](vrfhip_ctx* ctx, size_t lo, size_t hi) {
     BlobSlice m(msg, input ? nullptr : msg_off, msg_len, false, lo, hi), a(ad, ad_off, ad_len, true, lo, hi);
-    return vrfhip_pedersen_prove_batch(ctx, hi - lo, at32(sk, lo), m.blob, m.off, msg_len, input ? input + lo * pw : nullptr, a.blob, a.off,
-                                       ad_len, at_w(output, lo, w), at_w(pk_com, lo, w), at_w(r, lo, w), at_w(ok, lo, w), at32(s, lo),
-                                       at32(sb, lo), at32(blinding_out, lo), at_w(input_out, lo, pw),
+    return vrfhip_pedersen_prove_batch(ctx, hi - lo, at(sk, lo, 32), m.blob, m.off, msg_len, input ? input + lo * pw : nullptr, a.blob, a.off,
+                                       ad_len, at(output, lo, w), at(pk_com, lo, w), at(r, lo, w), at(ok, lo, w), at(s, lo, 32),
+                                       at(sb, lo, 32), at(blinding_out, lo, 32), at(input_out, lo, pw),
                                        status ? status + lo : nullptr);
   });
 }
@@ -2618,10 +2492,10 @@ int32_t vrfhip_pedersen_verify_batch_multi(vrfhip_ctx* const* ctxs, int32_t n_ct
     BlobSlice a(ad, ad_off, ad_len, true, lo, hi);
     if (rlc_seed)      // one multi-scalar multiplication per device slice; per-proof fallback inside the slice
       return vrfhip_pedersen_verify_batch_rlc(ctx, hi - lo, input + lo * pw, output + lo * pw, pk_com + lo * pw, r + lo * pw,
-                                              ok + lo * pw, at32(s, lo), at32(sb, lo), a.blob, a.off, ad_len, rlc_seed,
+                                              ok + lo * pw, at(s, lo, 32), at(sb, lo, 32), a.blob, a.off, ad_len, rlc_seed,
                                               status + lo, nullptr);
     return vrfhip_pedersen_verify_batch(ctx, hi - lo, input + lo * pw, output + lo * pw, pk_com + lo * pw, r + lo * pw,
-                                        ok + lo * pw, at32(s, lo), at32(sb, lo), a.blob, a.off, ad_len, status + lo);
+                                        ok + lo * pw, at(s, lo, 32), at(sb, lo, 32), a.blob, a.off, ad_len, status + lo);
   });
 }
 
@@ -2634,8 +2508,8 @@ int32_t vrfhip_ietf_verify_batch_affine_multi(vrfhip_ctx* const* ctxs, int32_t n
   if (!affine_ctxs_agree(ctxs, n_ctx)) return fail(VRFHIP_ERR_BAD_ARG, "contexts disagree on the suite or on VRFHIP_FLAG_COORDS_MONT256");
   return run_sharded(ctxs, n_ctx, n, [&](vrfhip_ctx* ctx, size_t lo, size_t hi) {
     BlobSlice a(ad, ad_off, ad_len, true, lo, hi);
-    return vrfhip_ietf_verify_batch_affine(ctx, hi - lo, pk_xy + lo * 64, input_xy + lo * 64, output_xy + lo * 64, at32(c, lo),
-                                           at32(s, lo), a.blob, a.off, ad_len, status + lo);
+    return vrfhip_ietf_verify_batch_affine(ctx, hi - lo, pk_xy + lo * 64, input_xy + lo * 64, output_xy + lo * 64, at(c, lo, 32),
+                                           at(s, lo, 32), a.blob, a.off, ad_len, status + lo);
   });
 }
 
@@ -2652,9 +2526,9 @@ int32_t vrfhip_pedersen_verify_batch_affine_multi(vrfhip_ctx* const* ctxs, int32
     const size_t o = lo * 64;
     if (rlc_seed)      // one multi-scalar multiplication per device slice; per-proof fallback inside the slice
       return vrfhip_pedersen_verify_batch_rlc_affine(ctx, hi - lo, input_xy + o, output_xy + o, pk_com_xy + o, r_xy + o, ok_xy + o,
-                                                     at32(s, lo), at32(sb, lo), a.blob, a.off, ad_len, rlc_seed, status + lo, nullptr);
+                                                     at(s, lo, 32), at(sb, lo, 32), a.blob, a.off, ad_len, rlc_seed, status + lo, nullptr);
     return vrfhip_pedersen_verify_batch_affine(ctx, hi - lo, input_xy + o, output_xy + o, pk_com_xy + o, r_xy + o, ok_xy + o,
-                                               at32(s, lo), at32(sb, lo), a.blob, a.off, ad_len, status + lo);
+                                               at(s, lo, 32), at(sb, lo, 32), a.blob, a.off, ad_len, status + lo);
   });
 }
 
