@@ -643,6 +643,53 @@ class Context:
             raise InvalidData()
         return out.tobytes()
 
+    def g1_decode_batch(self, points, check_subgroup: bool = True):
+        """`G1Affine::deserialize_compressed` on BLS12-381 (on the curve and, unless check_subgroup is False, in the
+        prime-order subgroup): points (n, 48) in the zcash / ark-bls12-381 form -> (xy (n, 96), status (n,)); an invalid
+        item's xy is all 0xFF, status 2."""
+        a = np.ascontiguousarray(points, dtype=np.uint8).reshape(-1, 48)
+        n = a.shape[0]
+        xy, st = np.empty((n, 96), np.uint8), np.empty(n, np.uint8)
+        _lib.check(self._lib.vrfhip_g1_decode_batch(self._h, n, _ptr(a) if n else None, int(check_subgroup),
+                                                    _ptr(xy) if n else None, _ptr(st) if n else None), "vrfhip_g1_decode_batch")
+        return xy, st
+
+    def g1_decode_batch_dev(self, points, xy, status, check_subgroup: bool = True, stream=None):
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _lib.check(self._lib.vrfhip_g1_decode_batch_dev(self._h, points.shape[0], points.data_ptr(), int(check_subgroup),
+                                                        xy.data_ptr(), status.data_ptr(), st), "vrfhip_g1_decode_batch_dev")
+
+    def g1_validate_batch(self, xy) -> np.ndarray:
+        """Affine BLS12-381 G1 points (n, 96): status 0 where the point is on the curve and in the prime-order subgroup."""
+        a = np.ascontiguousarray(xy, dtype=np.uint8).reshape(-1, 96)
+        n = a.shape[0]
+        st = np.empty(n, np.uint8)
+        _lib.check(self._lib.vrfhip_g1_validate_batch(self._h, n, _ptr(a) if n else None, _ptr(st) if n else None),
+                   "vrfhip_g1_validate_batch")
+        return st
+
+    def g1_validate_batch_dev(self, xy, status, stream=None):
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _lib.check(self._lib.vrfhip_g1_validate_batch_dev(self._h, xy.shape[0], xy.data_ptr(), status.data_ptr(), st),
+                   "vrfhip_g1_validate_batch_dev")
+
+    def g1_encode_batch(self, xy):
+        """Affine BLS12-381 G1 points (n, 96) -> (points (n, 48) compressed, status (n,)); no subgroup test."""
+        a = np.ascontiguousarray(xy, dtype=np.uint8).reshape(-1, 96)
+        n = a.shape[0]
+        out, st = np.empty((n, 48), np.uint8), np.empty(n, np.uint8)
+        _lib.check(self._lib.vrfhip_g1_encode_batch(self._h, n, _ptr(a) if n else None, _ptr(out) if n else None,
+                                                    _ptr(st) if n else None), "vrfhip_g1_encode_batch")
+        return out, st
+
+    def g1_encode_batch_dev(self, xy, points, status, stream=None):
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _lib.check(self._lib.vrfhip_g1_encode_batch_dev(self._h, xy.shape[0], xy.data_ptr(), points.data_ptr(),
+                                                        status.data_ptr(), st), "vrfhip_g1_encode_batch_dev")
+
     def hash_to_curve_batch(self, msgs) -> np.ndarray:
         if isinstance(msgs, np.ndarray):
             m = np.ascontiguousarray(msgs, dtype=np.uint8)

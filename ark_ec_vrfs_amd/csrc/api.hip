@@ -1939,6 +1939,85 @@ int32_t vrfhip_pairing_check_batch_rlc(vrfhip_ctx* ctx, size_t n, const uint8_t*
   return VRFHIP_SUCCESS;
 }
 
+// ------------------------------------------------------------------------- G1 codec (k_g1_codec.hip)
+// No workspace and nothing of the suite: the calls work on a context of any suite.  in_w / out_w: bytes per item of the
+// input and output arrays (out_w = 0: status only).
+}  // extern "C"
+
+namespace {
+template <class F>
+int32_t g1_codec_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_in, size_t in_w, uint8_t* d_out, size_t out_w,
+                     uint8_t* d_status, void* stream, F launch) {
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (n == 0) return VRFHIP_SUCCESS;
+  if (!d_in || (out_w && !d_out) || !d_status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  for_chunks(n, G1_CODEC_CHUNK, [&](size_t base, size_t m) -> int32_t {
+    launch(m, d_in + base * in_w, at(d_out, base, out_w), d_status + base, static_cast<hipStream_t>(stream));
+    return VRFHIP_SUCCESS;
+  });
+  HIP_TRY(hipGetLastError());
+  return VRFHIP_SUCCESS;
+}
+template <class F>
+int32_t g1_codec_host(vrfhip_ctx* ctx, size_t n, const uint8_t* in, size_t in_w, uint8_t* out, size_t out_w, uint8_t* status,
+                      F dev_call) {
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (n == 0) return VRFHIP_SUCCESS;
+  if (!in || (out_w && !out) || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  uint8_t *d_in, *d_out, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) { d_in = sg.take(n * in_w); d_out = sg.take(n * out_w); d_st = sg.take(n); });
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(d_in, in, n * in_w, hipMemcpyHostToDevice, ctx->stream));
+  rc = dev_call(d_in, d_out, d_st);
+  if (rc) return rc;
+  if (out_w) HIP_TRY(hipMemcpyAsync(out, d_out, n * out_w, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t vrfhip_g1_decode_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_points48, int32_t check_subgroup,
+                                   uint8_t* d_g1_xy, uint8_t* d_status, void* stream) {
+  return g1_codec_dev(ctx, n, d_points48, 48, d_g1_xy, 96, d_status, stream,
+                      [&](size_t m, const uint8_t* in, uint8_t* out, uint8_t* st, hipStream_t s) {
+                        launch_g1_decode(m, in, check_subgroup != 0, out, st, s);
+                      });
+}
+int32_t vrfhip_g1_decode_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* points48, int32_t check_subgroup, uint8_t* g1_xy,
+                               uint8_t* status) {
+  return g1_codec_host(ctx, n, points48, 48, g1_xy, 96, status, [&](const uint8_t* d_in, uint8_t* d_out, uint8_t* d_st) {
+    return vrfhip_g1_decode_batch_dev(ctx, n, d_in, check_subgroup, d_out, d_st, ctx->stream);
+  });
+}
+int32_t vrfhip_g1_validate_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_g1_xy, uint8_t* d_status, void* stream) {
+  return g1_codec_dev(ctx, n, d_g1_xy, 96, nullptr, 0, d_status, stream,
+                      [&](size_t m, const uint8_t* in, uint8_t*, uint8_t* st, hipStream_t s) { launch_g1_validate(m, in, st, s); });
+}
+int32_t vrfhip_g1_validate_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* g1_xy, uint8_t* status) {
+  return g1_codec_host(ctx, n, g1_xy, 96, nullptr, 0, status, [&](const uint8_t* d_in, uint8_t*, uint8_t* d_st) {
+    return vrfhip_g1_validate_batch_dev(ctx, n, d_in, d_st, ctx->stream);
+  });
+}
+int32_t vrfhip_g1_encode_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_g1_xy, uint8_t* d_points48, uint8_t* d_status,
+                                   void* stream) {
+  return g1_codec_dev(ctx, n, d_g1_xy, 96, d_points48, 48, d_status, stream,
+                      [&](size_t m, const uint8_t* in, uint8_t* out, uint8_t* st, hipStream_t s) {
+                        launch_g1_encode(m, in, out, st, s);
+                      });
+}
+int32_t vrfhip_g1_encode_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* g1_xy, uint8_t* points48, uint8_t* status) {
+  return g1_codec_host(ctx, n, g1_xy, 96, points48, 48, status, [&](const uint8_t* d_in, uint8_t* d_out, uint8_t* d_st) {
+    return vrfhip_g1_encode_batch_dev(ctx, n, d_in, d_out, d_st, ctx->stream);
+  });
+}
+
 // Test-only: quad-distributed Fp12 tower operations against the one-lane operations (k_pairing.hip)
 int32_t vrfhip_test_pairing_quad_ops(vrfhip_ctx* ctx, size_t n, const uint8_t* fp12_pairs, uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");

@@ -47,4 +47,11 @@ void launch_g1_rlc(const G1MsmLayout& L, const uint8_t* g1, const uint8_t seed[3
 // status1[0] = 0 / 2 (a coordinate >= p, a point off the curve or a scalar >= r).  L: sets = 1, windows = 26.
 void launch_g1_msm(const G1MsmLayout& L, const uint8_t* bases, const uint8_t* scalars, uint8_t* status1, hipStream_t st);
 
+// G1 codec (k_g1_codec.hip, g1_codec.cuh), one lane per point, no workspace; all arrays 4-byte aligned device memory.
+// points48: n x 48 B compressed (zcash / ark-bls12-381 form); g1_xy: n x 96 B affine as above; status[i] = 0 / 2.
+constexpr size_t G1_CODEC_CHUNK = size_t(1) << 20;       // items per launch
+void launch_g1_decode(size_t n, const uint8_t* points48, bool check_subgroup, uint8_t* g1_xy, uint8_t* status, hipStream_t st);
+void launch_g1_validate(size_t n, const uint8_t* g1_xy, uint8_t* status, hipStream_t st);
+void launch_g1_encode(size_t n, const uint8_t* g1_xy, uint8_t* points48, uint8_t* status, hipStream_t st);
+
 }  // namespace vrf

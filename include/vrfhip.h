@@ -50,21 +50,22 @@ extern "C" {
 typedef enum vrfhip_suite {
   VRFHIP_SUITE_BANDERSNATCH_SHA512_ELL2 = 1, /* `suites::bandersnatch` (src/lib.rs:14) */
   /* `suites::jubjub`: a = -1, cofactor 8, try-and-increment hash-to-curve.  Suite string, TAI
-   * details and the Pedersen blinding base are recollections: parity unpinned.  The built-in
-   * descriptor uses the suite string "JubJub_SHA-512_TAI" and, as blinding base, the TAI hash of
-   * "vrfhip-jubjub-blinding-base" -- a caller that knows the upstream constants supplies them through
-   * vrfhip_ctx_create_desc. */
+   * details are recollections: parity unpinned.  The built-in descriptor uses the suite string
+   * "JubJub_SHA-512_TAI" and carries NO Pedersen blinding base (vrfhip_pedersen_* answer VRFHIP_ERR_UNSUPPORTED): a caller
+   * supplies upstream's `BLINDING_BASE` through vrfhip_ctx_create_desc; the placeholder the tests use, the TAI hash of
+   * "vrfhip-jubjub-blinding-base", is available by name only (vrfhip_test_blinding_base). */
   VRFHIP_SUITE_JUBJUB_SHA512_TAI = 2,
   /* `suites::ed25519` ("Ed25519_SHA-512_TAI"): edwards25519 over 2^255 - 19, cofactor 8, try-and-increment, ArkworksCodec,
-   * `CHALLENGE_LEN = 16`.  The suite string, the challenge length and the (absent) salt are recollections of upstream and the
-   * built-in blinding base is the TAI hash of "vrfhip-ed25519-blinding-base": parity with upstream unpinned.  The SAME
+   * `CHALLENGE_LEN = 16`.  The suite string, the challenge length and the (absent) salt are recollections of upstream: parity
+   * with upstream unpinned; the built-in descriptor carries NO blinding base (as for JubJub; vrfhip_test_blinding_base names
+   * the placeholder, the TAI hash of "vrfhip-ed25519-blinding-base").  The SAME
    * kernels run RFC 9381's ECVRF-EDWARDS25519-SHA512-TAI when the descriptor says so (suite string 0x03, the three
    * VRFHIP_SUITE_FLAG_* below, the public key prepended to the message as salt), and that suite's published vectors
    * (RFC 9381 Appendix B.3) are golden vectors of this library: tests/golden/rfc9381_edwards25519_sha512_tai.json. */
   VRFHIP_SUITE_ED25519_SHA512_TAI = 3,
   /* `suites::baby_jubjub` ("BabyJubJub_SHA-512_TAI"): ark-ed-on-bn254 (a = 1, d = 168696/168700 over BN254 Fr), cofactor 8,
-   * try-and-increment, `CHALLENGE_LEN = 32`.  Suite string and blinding base as for JubJub: recollection / built-in TAI
-   * point, replaceable through the descriptor; parity unpinned. */
+   * try-and-increment, `CHALLENGE_LEN = 32`.  Suite string and blinding base as for JubJub: a recollection / none built in,
+   * supplied through the descriptor; parity unpinned. */
   VRFHIP_SUITE_BABY_JUBJUB_SHA512_TAI = 4,
   /* `suites::secp256r1` ("P256_SHA256_TAI" = RFC 9381's ECVRF-P256-SHA256-TAI, suite_string 0x01): NIST P-256, a short
    * Weierstrass curve of prime order (cofactor 1), SHA-256, `Sec1Codec`, `nonce_rfc_6979`, try-and-increment,
@@ -76,8 +77,8 @@ typedef enum vrfhip_suite {
    * vrfhip_ietf_prove_batch / _verify_batch (+ _dev, _multi), vrfhip_ietf_verify_batch_alpha, vrfhip_hash_to_curve_batch, vrfhip_output_hash_batch,
    * vrfhip_secret_from_seed_batch, vrfhip_point_validate_batch (+ _dev), and the Pedersen scheme per proof:
    * vrfhip_pedersen_prove_batch / vrfhip_pedersen_verify_batch (+ _dev, _multi) when the descriptor carries a blinding base
-   * (the built-in one is a nothing-up-my-sleeve point: upstream's `BLINDING_BASE` for this suite is not known here; a
-   * descriptor with an all-zero base makes a context without the scheme).  The x || y forms work as for the other suites
+   * (none is built in: upstream's `BLINDING_BASE` for this suite is not known here, and a descriptor with an all-zero base --
+   * the default -- makes a context without the scheme; vrfhip_test_blinding_base names a nothing-up-my-sleeve placeholder).  The x || y forms work as for the other suites
    * (vrfhip_ietf_verify_batch_affine; VRFHIP_FLAG_PROVE_POINTS_AFFINE for the provers' Gamma / pk / pk_com / R / Ok;
    * VRFHIP_FLAG_COORDS_MONT256; always little-endian, as arkworks holds coordinates in memory).  Since round 4 also vrfhip_msm, the batched
    * Pedersen verifier (vrfhip_pedersen_verify_batch_rlc, both forms) and key sets: every entry point exists on this suite.  Pinned by RFC 9381 Appendix B.1, which upstream's own
@@ -482,7 +483,8 @@ int32_t vrfhip_msm_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_bases_xy, con
  * An all-zero encoding is the point at infinity.  status[i]: 0 = product is one,
  * 1 = VerificationFailure, 2 = InvalidData (coordinate >= p or point off its curve).
  * Subgroup membership of the G1 / G2 inputs is the caller's precondition, as for arkworks' prepared
- * points. */
+ * points: for G1 it is established by vrfhip_g1_decode_batch, from the 48-byte wire form, or by
+ * vrfhip_g1_validate_batch, from these 96-byte points; their _dev forms chain in front of this call on one stream. */
 int32_t vrfhip_pairing_check_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2,
                                    int32_t g2_shared, uint8_t* status);
 int32_t vrfhip_pairing_check_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_g1,
@@ -496,7 +498,10 @@ int32_t vrfhip_pairing_check_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t*
  * two G1 multi-scalar multiplications (Pippenger, buckets in LDS) and ONE pairing check for the whole batch -- the
  * aggregation step in front of the pairing tail of `ring::Verifier::verify` (src/lib.rs:14).  g1: n x 192 B as above.
  * `seed`: 32 bytes unpredictable to whoever made the items; a batch holding a false item passes with probability
- * <= 2^-128 (the G1 points lie in the prime-order subgroup: the caller's precondition, as for arkworks' `G1Prepared`).
+ * <= 2^-128 PROVIDED the G1 points lie in the prime-order subgroup (the weights are 128 bits wide; a component of small
+ * order survives them with probability 1 / order).  That is the caller's precondition, as for arkworks' `G1Prepared`;
+ * vrfhip_g1_decode_batch / vrfhip_g1_validate_batch establish it (their invalid items come out as all-0xFF points, which
+ * this call answers with InvalidData).
  * _dev form: d_status[i] = 0 (part of the batch) or 2 (InvalidData: left out); d_verdict[0] = 0 if the batch equation
  * holds, 1 if it does not (vrfhip_pairing_check_batch_dev names the item), 2 if the shared pair is invalid.
  * Host form: the same per-item statuses as vrfhip_pairing_check_batch with g2_shared = 1 (a failing batch is
@@ -509,11 +514,41 @@ int32_t vrfhip_pairing_check_batch_rlc_dev(vrfhip_ctx* ctx, size_t n, const uint
 /* `VariableBaseMSM::msm` on BLS12-381 G1 (ark-bls12-381; the KZG commitment / aggregation primitive of the ring
  * suite): out = sum_i scalars[i] * bases[i].  bases: n x 96 B (x || y, 48-byte little-endian; all-zero = infinity);
  * scalars: n x 32 B little-endian, < r; out: 96 B in the same form; status: 1 byte, 0 = Ok, 2 = InvalidData (a
- * coordinate >= p, a point off the curve or a scalar >= r; out is then zeroed by the host form).  n = 0: infinity. */
+ * coordinate >= p, a point off the curve or a scalar >= r; out is then zeroed by the host form).  n = 0: infinity.
+ * No subgroup test: bases that come from the wire go through vrfhip_g1_decode_batch / vrfhip_g1_validate_batch first. */
 int32_t vrfhip_g1_msm(vrfhip_ctx* ctx, size_t n, const uint8_t* bases, const uint8_t* scalars, uint8_t* out,
                       uint8_t* status);
 int32_t vrfhip_g1_msm_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_bases, const uint8_t* d_scalars, uint8_t* d_out,
                           uint8_t* d_status, void* stream);
+
+/* BLS12-381 G1 points from and to the wire -- `G1Affine::deserialize_compressed` (arkworks' checked semantics: on the
+ * curve AND in the prime-order subgroup), `G1Affine::check` and `serialize_compressed` of ark-bls12-381, one lane per point:
+ * what every G1 element of a ring proof and every commitment of a verifier key goes through before the calls above.
+ * points48: n x 48 B in the zcash / ark-bls12-381 compressed form -- x as a big-endian integer; bit 7 of byte 0 =
+ * compressed, bit 6 = infinity, bit 5 = y is the larger of {y, p - y}.  g1_xy: n x 96 B, x || y as 48-byte little-endian
+ * canonical integers, all-zero = infinity (the form the pairing and MSM calls read).  status[i]: 0 = Ok, 2 = InvalidData.
+ *   decode:   InvalidData when the compressed bit is clear, the infinity bit comes with the sort bit or with any non-zero
+ *             bit of x, x >= p, x^3 + 4 is not a square, or (check_subgroup != 0) the point is outside the subgroup of order
+ *             r.  An invalid item's 96 output bytes are all 0xFF -- never zero, which would read as infinity downstream: a
+ *             caller that chains the _dev calls and ignores this status still gets InvalidData from the next call.
+ *             check_subgroup = 0 is arkworks' `deserialize_compressed_unchecked`.
+ *   validate: coordinates < p, on the curve, in the subgroup (infinity is valid).
+ *   encode:   InvalidData (and 48 bytes of 0xFF) for a coordinate >= p or a point off the curve; infinity -> 0xC0 00...;
+ *             no subgroup test.
+ * The subgroup test is the endomorphism test arkworks uses for this curve (phi(P) = -[x^2] P).  DEVIATION, deliberate:
+ * the infinity rule is the strict zcash one; ark-bls12-381 0.4, as far as is recalled, returns infinity as soon as the
+ * flag is set without looking at the remaining bytes.
+ * Work on a context of any suite; device arrays 4-byte aligned; n = 0 touches nothing; batches of any size (launches of
+ * 2^20 items). */
+int32_t vrfhip_g1_decode_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* points48, int32_t check_subgroup, uint8_t* g1_xy,
+                               uint8_t* status);
+int32_t vrfhip_g1_decode_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_points48, int32_t check_subgroup,
+                                   uint8_t* d_g1_xy, uint8_t* d_status, void* stream);
+int32_t vrfhip_g1_validate_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* g1_xy, uint8_t* status);
+int32_t vrfhip_g1_validate_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_g1_xy, uint8_t* d_status, void* stream);
+int32_t vrfhip_g1_encode_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* g1_xy, uint8_t* points48, uint8_t* status);
+int32_t vrfhip_g1_encode_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_g1_xy, uint8_t* d_points48, uint8_t* d_status,
+                                   void* stream);
 
 /* Building blocks --------------------------------------------------------------------- */
 

@@ -508,7 +508,55 @@ def bls_constants():
         return r
     gam = [f2pow((1, 1), (P - 1) * i // 6) for i in range(6)]
     return dict(P=P, lim=lim, mont=mont, bias=bias, gam=gam, NLB=NLB, WB=WB,
-                pinv=(-pow(P, -1, 1 << WB)) % (1 << WB))
+                pinv=(-pow(P, -1, 1 << WB)) % (1 << WB), beta=bls_g1_beta(P))
+
+
+def bls_g1_beta(P):
+    """The cube root of unity beta of Fp with phi(x, y) = (beta x, y) = -[x^2] P on the prime-order subgroup of
+    G1: y^2 = x^3 + 4 (x = -0xD201000000010000 the curve parameter): the constant of the subgroup test of g1_codec.cuh.
+    Both primitive roots are tried on the generator; exactly one may pass."""
+    X_ABS = 0xD201000000010000
+    r = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+    G = (0x17F1D3A73197D7942695638C4FA9AC0FC3688C4F9774B905A14E3A3F171BAC586C55E83FF97A1AEFFB3AF00ADB22C6BB,
+         0x08B3F481E3AAA0F1A09E30ED741D8AE4FCF5E095D5D00AF600DB18CB2C04B3EDD03CC744A2888AE40CAA232946C5E7E1)
+    assert X_ABS ** 4 - X_ABS ** 2 + 1 == r and P % 4 == 3 and P % 3 == 1
+    assert (G[1] * G[1] - G[0] ** 3 - 4) % P == 0, "G1 generator not on the curve"
+
+    def add(p1, p2):                          # affine, None = infinity (a = 0)
+        if p1 is None:
+            return p2
+        if p2 is None:
+            return p1
+        if p1[0] == p2[0]:
+            if (p1[1] + p2[1]) % P == 0:
+                return None
+            lam = 3 * p1[0] * p1[0] * pow(2 * p1[1], -1, P) % P
+        else:
+            lam = (p2[1] - p1[1]) * pow(p2[0] - p1[0], -1, P) % P
+        x = (lam * lam - p1[0] - p2[0]) % P
+        return (x, (lam * (p1[0] - x) - p1[1]) % P)
+
+    def mul(k, pt):
+        acc = None
+        for bit in bin(k)[2:]:
+            acc = add(acc, acc)
+            if bit == "1":
+                acc = add(acc, pt)
+        return acc
+    assert mul(r, G) is None, "G1 generator order"
+    x2G = mul(X_ABS * X_ABS, G)
+    want = (x2G[0], (-x2G[1]) % P)            # -[x^2] G
+    g = 2
+    while pow(g, (P - 1) // 3, P) == 1:
+        g += 1
+    b1 = pow(g, (P - 1) // 3, P)
+    roots = [b1, b1 * b1 % P]
+    assert all((b * b + b + 1) % P == 0 for b in roots)
+    good = [b for b in roots if (b * G[0] % P, G[1]) == want]
+    assert len(good) == 1, "exactly one cube root of unity has the eigenvalue -x^2 on G1"
+    other = [b for b in roots if b != good[0]][0]
+    assert (other * G[0] % P, G[1]) != want, "the other root must fail"
+    return good[0]
 
 
 def xy_le(x, y):
@@ -708,6 +756,10 @@ def gen_field0():
     for i in range(1, 6):
         ap(carr("BLS_GAMMA%d_RE_M" % i, bl["lim"](bl["mont"](bl["gam"][i][0]))))
         ap(carr("BLS_GAMMA%d_IM_M" % i, bl["lim"](bl["mont"](bl["gam"][i][1]))))
+    ap("// G1 codec (g1_codec.cuh): the square-root exponent (p + 1) / 4 and the cube root of unity beta with")
+    ap("// (beta x, y) = -[x^2] (x, y) on the prime-order subgroup (checked on the generator; the other root fails)")
+    ap(carr("BLS_EXP_SQRT", [((bl["P"] + 1) // 4 >> (32 * i)) & 0xFFFFFFFF for i in range(12)]))
+    ap(carr("BLS_BETA_M", bl["lim"](bl["mont"](bl["beta"]))))
     emit_field_traits(ap, F, st)
     emit_tables(ap, F, st, [("BS_G_XY", (BS["gx"], BS["gy"])), ("BS_B_XY", (BS["bx"], BS["by"])),
                             ("JJ_G_XY", (JJ["gx"], JJ["gy"])), ("JJ_B_XY", (jbx, jby))])
