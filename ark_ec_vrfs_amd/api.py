@@ -690,6 +690,39 @@ class Context:
         _lib.check(self._lib.vrfhip_g1_encode_batch_dev(self._h, xy.shape[0], xy.data_ptr(), points.data_ptr(),
                                                         status.data_ptr(), st), "vrfhip_g1_encode_batch_dev")
 
+    def g1_lincomb_batch(self, bases, scalars, shared_bases=None, shared_scalars=None):
+        """Per-item linear combinations on BLS12-381 G1: out[i] = sum_j scalars[i][j] bases[i][j] + sum_j shared_scalars[i][j]
+        shared_bases[j].  bases (n, k, 96) with scalars (n, k, 32), shared_bases (m, 96) with shared_scalars (n, m, 32); either
+        pair may be None; 1 <= k + m <= 16.  -> (out (n, 96), status (n,)); an invalid item's out is all 0xFF, status 2."""
+        u8 = lambda a, *shape: None if a is None else np.ascontiguousarray(a, dtype=np.uint8).reshape(*shape)
+        if bases is None and shared_bases is None:
+            raise ValueError("no terms")
+        k = 0 if bases is None else np.shape(bases)[-2]
+        b, s = u8(bases, -1, k, 96), u8(scalars, -1, k, 32)
+        sb = u8(shared_bases, -1, 96)
+        m = 0 if sb is None else sb.shape[0]
+        ss = u8(shared_scalars, -1, m, 32)
+        n = b.shape[0] if k else ss.shape[0]
+        if (k and s.shape[0] != n) or (m and ss.shape[0] != n):
+            raise ValueError("ragged batch")
+        out, st = np.empty((n, 96), np.uint8), np.empty(n, np.uint8)
+        p = lambda a: _ptr(a) if a is not None and a.size else None
+        _lib.check(self._lib.vrfhip_g1_lincomb_batch(self._h, n, k, p(b), p(s), m, p(sb), p(ss), p(out), p(st)),
+                   "vrfhip_g1_lincomb_batch")
+        return out, st
+
+    def g1_lincomb_batch_dev(self, bases, scalars, shared_bases, shared_scalars, out, status, out_stride: int = 96, stream=None):
+        """Device form: tensors bases (n, k, 96) / scalars (n, k, 32) and shared_bases (m, 96) / shared_scalars (n, m, 32),
+        either pair None; the result of item i goes to out.data_ptr() + i * out_stride (a view into the (n, 192) item array
+        of the pairing calls with out_stride = 192 chains the two on one stream); status (n,)."""
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        dp = lambda t: None if t is None else t.data_ptr()
+        k, m = 0 if bases is None else bases.shape[1], 0 if shared_bases is None else shared_bases.shape[0]
+        _lib.check(self._lib.vrfhip_g1_lincomb_batch_dev(self._h, status.shape[0], k, dp(bases), dp(scalars), m, dp(shared_bases),
+                                                         dp(shared_scalars), dp(out), out_stride, dp(status), st),
+                   "vrfhip_g1_lincomb_batch_dev")
+
     def hash_to_curve_batch(self, msgs) -> np.ndarray:
         if isinstance(msgs, np.ndarray):
             m = np.ascontiguousarray(msgs, dtype=np.uint8)

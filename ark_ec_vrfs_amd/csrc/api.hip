@@ -2018,6 +2018,77 @@ int32_t vrfhip_g1_encode_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* g1_xy, 
   });
 }
 
+// ------------------------------------------------------------------------- G1 linear combinations (k_g1_lincomb.hip)
+// Like the codec: no workspace, nothing of the suite.
+}  // extern "C"
+
+namespace {
+// the argument rules both forms share: the counts first, then n = 0 (nothing is touched, NULLs are fine), then the arrays --
+// one whose count is 0 may be NULL.  *empty: the call is done.
+int32_t g1_lincomb_args(vrfhip_ctx* ctx, size_t n, uint32_t k, const uint8_t* bases, const uint8_t* scalars, uint32_t m,
+                        const uint8_t* shared_bases, const uint8_t* shared_scalars, const uint8_t* out, size_t out_stride,
+                        const uint8_t* status, bool* empty) {
+  *empty = n == 0;
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (k > 16 || m > 16 || k + m < 1 || k + m > 16) return fail(VRFHIP_ERR_BAD_ARG, "k + m must be in 1..16");
+  if (out_stride < 96 || out_stride % 4) return fail(VRFHIP_ERR_BAD_ARG, "out_stride must be >= 96 and a multiple of 4");
+  if (n == 0) return VRFHIP_SUCCESS;
+  if ((k && (!bases || !scalars)) || (m && (!shared_bases || !shared_scalars)) || !out || !status)
+    return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  return VRFHIP_SUCCESS;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t vrfhip_g1_lincomb_batch_dev(vrfhip_ctx* ctx, size_t n, uint32_t k, const uint8_t* d_bases, const uint8_t* d_scalars,
+                                    uint32_t m, const uint8_t* d_shared_bases, const uint8_t* d_shared_scalars, uint8_t* d_out,
+                                    size_t out_stride, uint8_t* d_status, void* stream) {
+  bool empty;
+  int32_t rc = g1_lincomb_args(ctx, n, k, d_bases, d_scalars, m, d_shared_bases, d_shared_scalars, d_out, out_stride, d_status,
+                               &empty);
+  if (rc || empty) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  for_chunks(n, G1_LINCOMB_CHUNK, [&](size_t base, size_t cnt) -> int32_t {
+    launch_g1_lincomb(cnt, k, at(d_bases, base, size_t(k) * 96), at(d_scalars, base, size_t(k) * 32), m, d_shared_bases,
+                      at(d_shared_scalars, base, size_t(m) * 32), d_out + base * out_stride, out_stride, d_status + base,
+                      static_cast<hipStream_t>(stream));
+    return VRFHIP_SUCCESS;
+  });
+  HIP_TRY(hipGetLastError());
+  return VRFHIP_SUCCESS;
+}
+int32_t vrfhip_g1_lincomb_batch(vrfhip_ctx* ctx, size_t n, uint32_t k, const uint8_t* bases, const uint8_t* scalars, uint32_t m,
+                                const uint8_t* shared_bases, const uint8_t* shared_scalars, uint8_t* out, uint8_t* status) {
+  bool empty;
+  int32_t rc = g1_lincomb_args(ctx, n, k, bases, scalars, m, shared_bases, shared_scalars, out, 96, status, &empty);
+  if (rc || empty) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  uint8_t *d_b, *d_s, *d_sb, *d_ss, *d_out, *d_st;
+  rc = stage_layout(ctx, [&](Stage& sg) {
+    d_b = sg.take(n * k * 96); d_s = sg.take(n * k * 32);
+    d_sb = sg.take(size_t(m) * 96); d_ss = sg.take(n * m * 32);
+    d_out = sg.take(n * 96); d_st = sg.take(n);
+  });
+  if (rc) return rc;
+  if (k) {
+    HIP_TRY(hipMemcpyAsync(d_b, bases, n * k * 96, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_s, scalars, n * k * 32, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (m) {
+    HIP_TRY(hipMemcpyAsync(d_sb, shared_bases, size_t(m) * 96, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_ss, shared_scalars, n * m * 32, hipMemcpyHostToDevice, ctx->stream));
+  }
+  rc = vrfhip_g1_lincomb_batch_dev(ctx, n, k, d_b, d_s, m, d_sb, d_ss, d_out, 96, d_st, ctx->stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, d_out, n * 96, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+
 // Test-only: quad-distributed Fp12 tower operations against the one-lane operations (k_pairing.hip)
 int32_t vrfhip_test_pairing_quad_ops(vrfhip_ctx* ctx, size_t n, const uint8_t* fp12_pairs, uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");

@@ -54,4 +54,14 @@ void launch_g1_decode(size_t n, const uint8_t* points48, bool check_subgroup, ui
 void launch_g1_validate(size_t n, const uint8_t* g1_xy, uint8_t* status, hipStream_t st);
 void launch_g1_encode(size_t n, const uint8_t* g1_xy, uint8_t* points48, uint8_t* status, hipStream_t st);
 
+// Per-item linear combinations (k_g1_lincomb.hip, g1_lincomb.cuh), one lane per term, no workspace:
+// out[i] = sum_{j<k} scalars[i][j] bases[i][j] + sum_{j<m} shared_scalars[i][j] shared_bases[j], 1 <= k + m <= 16.
+// bases: n x k x 96 B, scalars: n x k x 32 B, shared_bases: m x 96 B, shared_scalars: n x m x 32 B (an array whose count is
+// 0 is not read); the result of item i: 96 B at out + i * out_stride; status[i] = 0 / 2.  All arrays 4-byte aligned.
+constexpr size_t G1_LINCOMB_CHUNK = size_t(1) << 20;     // items per launch
+constexpr int G1_LINCOMB_BLOCK = 128;                    // lanes per workgroup: a multiple of every group size 1 .. 16
+void launch_g1_lincomb(size_t n, uint32_t k, const uint8_t* bases, const uint8_t* scalars, uint32_t m,
+                       const uint8_t* shared_bases, const uint8_t* shared_scalars, uint8_t* out, size_t out_stride,
+                       uint8_t* status, hipStream_t st);
+
 }  // namespace vrf

@@ -550,6 +550,31 @@ int32_t vrfhip_g1_encode_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* g1_xy, 
 int32_t vrfhip_g1_encode_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_g1_xy, uint8_t* d_points48, uint8_t* d_status,
                                    void* stream);
 
+/* Per-item linear combinations of BLS12-381 G1 points -- the step between the two calls above and the pairing check in a
+ * verifier that opens polynomial commitments: per proof i, A_i = sum s_ij C_ij + sum t_ij S_j and B_i = sum u_ij pi_ij, in
+ * arkworks a `VariableBaseMSM::msm` over about a dozen points each.
+ *     out[i] = sum_{j<k} scalars[i][j] * bases[i][j] + sum_{j<m} shared_scalars[i][j] * shared_bases[j]
+ * bases: n x k x 96 B, the item's own points; shared_bases: m x 96 B, used by every item (a verifier key's commitments, the
+ * generator); scalars: n x k x 32 B and shared_scalars: n x m x 32 B.  1 <= k + m <= 16; k or m may be 0, and an array whose
+ * count is 0 may be NULL.  Formats as for vrfhip_g1_msm: a point is x || y, 48-byte little-endian canonical each, all-zero =
+ * infinity; a scalar is 32-byte little-endian and < r.  out: n x 96 B.  A base at infinity and a zero scalar are valid
+ * terms; a sum that is infinity comes out all-zero.
+ * status[i]: 0 = Ok, 2 = InvalidData -- a coordinate >= p, a point off the curve or a scalar >= r among the terms of item
+ * i; an invalid shared base makes every item InvalidData.  An invalid item's 96 output bytes are all 0xFF (the codec's rule:
+ * a chained pairing call then answers InvalidData and cannot read the result as infinity).
+ * No subgroup test, as for vrfhip_g1_msm: wire inputs go through vrfhip_g1_decode_batch / vrfhip_g1_validate_batch first.
+ * _dev form: out_stride is the byte distance between results, >= 96 and a multiple of 4; the bytes between results are not
+ * touched.  With 192, two calls write A_i (at d_g1) and B_i (at d_g1 + 96) straight into the n x 192 item array of
+ * vrfhip_pairing_check_batch*_dev on the same stream.
+ * One lane per term and no workspace.  Work on a context of any suite; device arrays 4-byte aligned; n = 0 touches nothing;
+ * batches of any size (launches of 2^20 items).  VRFHIP_ERR_BAD_ARG: NULL where a count is non-zero, k + m outside 1..16, a
+ * bad out_stride. */
+int32_t vrfhip_g1_lincomb_batch(vrfhip_ctx* ctx, size_t n, uint32_t k, const uint8_t* bases, const uint8_t* scalars, uint32_t m,
+                                const uint8_t* shared_bases, const uint8_t* shared_scalars, uint8_t* out, uint8_t* status);
+int32_t vrfhip_g1_lincomb_batch_dev(vrfhip_ctx* ctx, size_t n, uint32_t k, const uint8_t* d_bases, const uint8_t* d_scalars,
+                                    uint32_t m, const uint8_t* d_shared_bases, const uint8_t* d_shared_scalars, uint8_t* d_out,
+                                    size_t out_stride, uint8_t* d_status, void* stream);
+
 /* Building blocks --------------------------------------------------------------------- */
 
 /* `Input::new(data)` = Suite::data_to_point = hash_to_curve_ell2_rfc_9380 (src/lib.rs:14-16):
