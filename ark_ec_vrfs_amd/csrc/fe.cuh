@@ -195,6 +195,23 @@ VRF_HD Fe<L, V> fe_select(bool c, const Fe<L, V>& a, const Fe<L, V>& b) {   // c
 
 // ------------------------------------------------------------------ multiply
 VRF_HD uint64_t mad(uint32_t a, uint32_t b, uint64_t c) { return (uint64_t)a * b + c; }
+// The multiply-add of the product columns.  Left alone, LLVM reassociates a column of fe_mul: it sums the a*b terms apart
+// from the carried accumulator, so that they need not wait for the Montgomery digits, and pays a 64-bit addition per column
+// to join the two (24 v_lshl_add_u64 per product where 9 are the bias).  CHAIN = true passes the result through an empty
+// asm on the device, which keeps every column the single multiply-add chain it is written as: 214 -> 198 VALU instructions
+// per product, 184 -> 169 per square, and a third fewer live registers -- but one dependent chain of 153 multiply-adds.
+// That pays in the verification ladders (straus2 / straus4 / win_mul, vrf_core.cuh), which it takes from three to four
+// waves per SIMD; it costs time in the kernels that sit at two waves with scratch whatever the product does (checked
+// decode: +2 %, measured), so CHAIN is an argument that only those ladders set.  The host build has
+// no such instruction to protect.
+template <bool CHAIN>
+VRF_HD uint64_t mac(uint32_t a, uint32_t b, uint64_t c) {
+  uint64_t r = (uint64_t)a * b + c;
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (CHAIN) asm("" : "+v"(r));
+#endif
+  return r;
+}
 // Three digit rules, chosen at compile time by the field (field.h, vrfk::FIELD_KIND):
 //
 //  kind 0 (BLS12-381 Fr, q = 1 mod 2^29): the Montgomery digit of a column t is m = -t mod 2^29 and the column leaves the
@@ -217,9 +234,10 @@ VRF_HD uint32_t mont_digit(uint32_t col) {
 constexpr uint32_t PM_FOLD = 1216;      // 2^261 mod (2^255 - 19)
 constexpr int PM_TOPBITS = 23;          // bit 255 is bit 23 of limb 8
 
-// second pass of the pseudo-Mersenne product: d = the plain product in 18 digits (d[17] < 2^29 because the operands are
-// < 64 q); digit k + 9 folds onto digit k with the factor 2^261 = 1216, and what then lies above bit 255 (bit 23 of
-// limb 8) comes back as 19 * carry into limb 0.  Out: limbs < 2^29 + 2, value < 2^255 + 2^30 < 2q.
+// second pass of the pseudo-Mersenne product: d = the plain product, or sum of two products, in 18 digits (d[17] < 2^29
+// because the sum is < 2^522: operands < 64 q in fe_mul, V1 V2 + V3 V4 <= 4096 asserted in fe_mul2); digit k + 9 folds
+// onto digit k with the factor 2^261 = 1216, and what then lies above bit 255 (bit 23 of limb 8) comes back as 19 * carry
+// into limb 0.  Out: limbs < 2^29 + 2, value < 2^255 + 2^30 < 2q.
 template <int V>
 VRF_HD void pm_fold(Fe<1, V>& r, const uint32_t (&d)[2 * NL]) {
   uint64_t acc = 0;
@@ -237,52 +255,82 @@ VRF_HD void pm_fold(Fe<1, V>& r, const uint32_t (&d)[2 * NL]) {
   r.v[1] += r0 >> LW;
 }
 
-template <int L1, int V1, int L2, int V2>
-VRF_HD Fe<1, mul_v(V1, V2)> fe_mul(const Fe<L1, V1>& a, const Fe<L2, V2>& b) {
-  static_assert(L1 * L2 <= 6, "fe_mul: 64-bit column accumulator could overflow");
-  Fe<1, mul_v(V1, V2)> r;
+// The columns of a*b (TWO = false) or of a*b + c*d (TWO = true: both products go into the same columns and the sum is
+// reduced ONCE), on raw limbs; V is the caller's value bound of the result.
+template <bool CHAIN, bool TWO, int V>
+VRF_HD Fe<1, V> fe_mul_cols(const uint32_t (&a)[NL], const uint32_t (&b)[NL], const uint32_t (&c)[NL], const uint32_t (&d)[NL]) {
+  Fe<1, V> r;
   if constexpr (vrfk::FIELD_KIND == 2) {
-    uint32_t d[2 * NL];                                   // the plain product in 29-bit digits: < 2^522
+    uint32_t dg[2 * NL];                                  // the plain product in 29-bit digits: < 2^522
     uint64_t acc = 0;
 #pragma unroll
     for (int k = 0; k < 2 * NL - 1; ++k) {
 #pragma unroll
-      for (int i = (k < NL ? 0 : k - NL + 1); i <= (k < NL ? k : NL - 1); ++i) acc = mad(a.v[i], b.v[k - i], acc);
-      d[k] = (uint32_t)acc & LMASK;
+      for (int i = (k < NL ? 0 : k - NL + 1); i <= (k < NL ? k : NL - 1); ++i) {
+        acc = mac<CHAIN>(a[i], b[k - i], acc);
+        if constexpr (TWO) acc = mac<CHAIN>(c[i], d[k - i], acc);
+      }
+      dg[k] = (uint32_t)acc & LMASK;
       acc >>= LW;
     }
-    d[2 * NL - 1] = (uint32_t)acc;
-    pm_fold(r, d);
-    return r;
+    dg[2 * NL - 1] = (uint32_t)acc;
+    pm_fold(r, dg);
   } else {
-  uint32_t m[NL];
-  uint64_t acc = 0;
+    uint32_t m[NL];
+    uint64_t acc = 0;
 #pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    acc += mont_bias();
+    for (int k = 0; k < NL; ++k) {
+      acc += mont_bias();
 #pragma unroll
-    for (int i = 0; i <= k; ++i) acc = mad(a.v[i], b.v[k - i], acc);
+      for (int i = 0; i <= k; ++i) {
+        acc = mac<CHAIN>(a[i], b[k - i], acc);
+        if constexpr (TWO) acc = mac<CHAIN>(c[i], d[k - i], acc);
+      }
 #pragma unroll
-    for (int i = 0; i < k; ++i) acc = mad(m[i], vrfk::Q29[k - i], acc);
-    m[k] = mont_digit((uint32_t)acc);
-    if constexpr (vrfk::FIELD_KIND != 0) acc = mad(m[k], vrfk::Q29[0], acc);
-    acc >>= LW;                        // kind 0: == (column + m[k] * Q29[0]) >> LW, Q29[0] == 1 (see mont_bias)
+      for (int i = 0; i < k; ++i) acc = mac<CHAIN>(m[i], vrfk::Q29[k - i], acc);
+      m[k] = mont_digit((uint32_t)acc);
+      if constexpr (vrfk::FIELD_KIND != 0) acc = mac<CHAIN>(m[k], vrfk::Q29[0], acc);
+      acc >>= LW;                        // kind 0: == (column + m[k] * Q29[0]) >> LW, Q29[0] == 1 (see mont_bias)
+    }
+#pragma unroll
+    for (int k = NL; k < 2 * NL - 1; ++k) {
+#pragma unroll
+      for (int i = k - NL + 1; i < NL; ++i) {
+        acc = mac<CHAIN>(a[i], b[k - i], acc);
+        if constexpr (TWO) acc = mac<CHAIN>(c[i], d[k - i], acc);
+      }
+#pragma unroll
+      for (int i = k - NL + 1; i < NL; ++i) acc = mac<CHAIN>(m[i], vrfk::Q29[k - i], acc);
+      r.v[k - NL] = (uint32_t)acc & LMASK;
+      acc >>= LW;
+    }
+    r.v[NL - 1] = (uint32_t)acc;
   }
-#pragma unroll
-  for (int k = NL; k < 2 * NL - 1; ++k) {
-#pragma unroll
-    for (int i = k - NL + 1; i < NL; ++i) acc = mad(a.v[i], b.v[k - i], acc);
-#pragma unroll
-    for (int i = k - NL + 1; i < NL; ++i) acc = mad(m[i], vrfk::Q29[k - i], acc);
-    r.v[k - NL] = (uint32_t)acc & LMASK;
-    acc >>= LW;
-  }
-  r.v[NL - 1] = (uint32_t)acc;
   return r;
-  }
 }
 
-template <int L, int V>
+template <bool CHAIN = false, int L1, int V1, int L2, int V2>
+VRF_HD Fe<1, mul_v(V1, V2)> fe_mul(const Fe<L1, V1>& a, const Fe<L2, V2>& b) {
+  static_assert(L1 * L2 <= 6, "fe_mul: 64-bit column accumulator could overflow");
+  return fe_mul_cols<CHAIN, false, mul_v(V1, V2)>(a.v, b.v, a.v, b.v);
+}
+
+// a*b + c*d with ONE reduction: 2 * 81 + 72 multiply-adds against two full products (2 * 153) plus a lazy addition.
+// The column bound is the one of fe_mul with L1 L2 + L3 L4 in the place of L1 L2: 9 (L1 L2 + L3 L4) 2^58 (1 + 2^-15)
+// + 9 * 2^58 + carry < 2^64 for a sum <= 6.  Value: (a b + c d + m q) / R < q (1 + (V1 V2 + V3 V4) q / R).
+// 2^255 - 19: the plain sum of the two products must stay below 2^522 for pm_fold's top digit d[17] < 2^29:
+// (V1 V2 + V3 V4) q^2 < 2^12 * 2^510; its result is < 2q whatever came in.
+constexpr int mul2_v(int v1, int v2, int v3, int v4) {
+  return vrfk::FIELD_KIND == 2 ? 2 : 1 + ((v1 * v2 + v3 * v4) * vrfk::MULV_NUM + 99999) / 100000;
+}
+template <bool CHAIN = false, int L1, int V1, int L2, int V2, int L3, int V3, int L4, int V4>
+VRF_HD Fe<1, mul2_v(V1, V2, V3, V4)> fe_mul2(const Fe<L1, V1>& a, const Fe<L2, V2>& b, const Fe<L3, V3>& c, const Fe<L4, V4>& d) {
+  static_assert(L1 * L2 + L3 * L4 <= 6, "fe_mul2: 64-bit column accumulator could overflow");
+  static_assert(vrfk::FIELD_KIND != 2 || V1 * V2 + V3 * V4 <= 4096, "fe_mul2: the plain sum of products must stay below 2^522");
+  return fe_mul_cols<CHAIN, true, mul2_v(V1, V2, V3, V4)>(a.v, b.v, c.v, d.v);
+}
+
+template <bool CHAIN = false, int L, int V>
 VRF_HD Fe<1, mul_v(V, V)> fe_sqr(const Fe<L, V>& a) {
   static_assert(L * L <= 6, "fe_sqr: 64-bit column accumulator could overflow");
   Fe<1, mul_v(V, V)> r;
@@ -295,8 +343,8 @@ VRF_HD Fe<1, mul_v(V, V)> fe_sqr(const Fe<L, V>& a) {
 #pragma unroll
     for (int k = 0; k < 2 * NL - 1; ++k) {
 #pragma unroll
-      for (int i = (k < NL ? 0 : k - NL + 1); 2 * i < k; ++i) acc = mad(a2[i], a.v[k - i], acc);
-      if ((k & 1) == 0) acc = mad(a.v[k / 2], a.v[k / 2], acc);
+      for (int i = (k < NL ? 0 : k - NL + 1); 2 * i < k; ++i) acc = mac<CHAIN>(a2[i], a.v[k - i], acc);
+      if ((k & 1) == 0) acc = mac<CHAIN>(a.v[k / 2], a.v[k / 2], acc);
       d[k] = (uint32_t)acc & LMASK;
       acc >>= LW;
     }
@@ -310,21 +358,21 @@ VRF_HD Fe<1, mul_v(V, V)> fe_sqr(const Fe<L, V>& a) {
   for (int k = 0; k < NL; ++k) {
     acc += mont_bias();
 #pragma unroll
-    for (int i = 0; 2 * i < k; ++i) acc = mad(a2[i], a.v[k - i], acc);
-    if ((k & 1) == 0) acc = mad(a.v[k / 2], a.v[k / 2], acc);
+    for (int i = 0; 2 * i < k; ++i) acc = mac<CHAIN>(a2[i], a.v[k - i], acc);
+    if ((k & 1) == 0) acc = mac<CHAIN>(a.v[k / 2], a.v[k / 2], acc);
 #pragma unroll
-    for (int i = 0; i < k; ++i) acc = mad(m[i], vrfk::Q29[k - i], acc);
+    for (int i = 0; i < k; ++i) acc = mac<CHAIN>(m[i], vrfk::Q29[k - i], acc);
     m[k] = mont_digit((uint32_t)acc);
-    if constexpr (vrfk::FIELD_KIND != 0) acc = mad(m[k], vrfk::Q29[0], acc);
+    if constexpr (vrfk::FIELD_KIND != 0) acc = mac<CHAIN>(m[k], vrfk::Q29[0], acc);
     acc >>= LW;
   }
 #pragma unroll
   for (int k = NL; k < 2 * NL - 1; ++k) {
 #pragma unroll
-    for (int i = k - NL + 1; 2 * i < k; ++i) acc = mad(a2[i], a.v[k - i], acc);
-    if ((k & 1) == 0) acc = mad(a.v[k / 2], a.v[k / 2], acc);
+    for (int i = k - NL + 1; 2 * i < k; ++i) acc = mac<CHAIN>(a2[i], a.v[k - i], acc);
+    if ((k & 1) == 0) acc = mac<CHAIN>(a.v[k / 2], a.v[k / 2], acc);
 #pragma unroll
-    for (int i = k - NL + 1; i < NL; ++i) acc = mad(m[i], vrfk::Q29[k - i], acc);
+    for (int i = k - NL + 1; i < NL; ++i) acc = mac<CHAIN>(m[i], vrfk::Q29[k - i], acc);
     r.v[k - NL] = (uint32_t)acc & LMASK;
     acc >>= LW;
   }

@@ -3,7 +3,8 @@
 // Replaces ark_ec::twisted_edwards::{Affine, Projective} add / double / mul_bigint behind
 // `AffinePoint` (/root/reference src/lib.rs:15) for the two suites on the hot path:
 // Bandersnatch (a = -5) and JubJub (a = -1).  Formulas: add-2008-hwcd (unified) and
-// dbl-2008-hwcd, rewritten so that a = -ANEG never needs a negation.  Every intermediate
+// dbl-2008-hwcd, rewritten so that a = -ANEG never needs a negation; the addition forms its E and H as fused sums of two
+// products with one reduction each (fe_mul2) instead of three reduced products.  Every intermediate
 // carries its (L, V) bound (fe.cuh); the closure bound for point coordinates is FeP = Fe<1,5>.
 //
 // Exceptional cases: a is a non-square for both curves, so the unified law is complete on the
@@ -131,12 +132,14 @@ VRF_HD PtC ptc_load(const uint32_t* m) {
 
 // 2P.  need_t = false skips the T coordinate (legal when the next operation is a doubling);
 // it is wave-uniform at every call site, so the branch is scalar.
-template <class C>
+// CHAIN (here and in the additions): every product a single multiply-add chain (fe.cuh: mac); set by the verification
+// ladders only.
+template <class C, bool CHAIN = false>
 VRF_HD PtE te_dbl(const PtE& p, bool need_t) {
-  auto A = fe_sqr(p.X);                               // (1,2)
-  auto B = fe_sqr(p.Y);                               // (1,2)
-  auto S = fe_sqr(fe_add(p.X, p.Y));                  // (1,3)
-  auto ZZ = fe_sqr(p.Z);                              // (1,2)
+  auto A = fe_sqr<CHAIN>(p.X);                               // (1,2)
+  auto B = fe_sqr<CHAIN>(p.Y);                               // (1,2)
+  auto S = fe_sqr<CHAIN>(fe_add(p.X, p.Y));                  // (1,3)
+  auto ZZ = fe_sqr<CHAIN>(p.Z);                              // (1,2)
   PtE r;
   if constexpr (C::A_PLUS_ONE) {
     // a = 1: E = 2XY = S - A - B, G = A + B, F = G - 2Z^2, H = A - B; X3 = E F, Y3 = G H, Z3 = F G, T3 = E H
@@ -144,31 +147,36 @@ VRF_HD PtE te_dbl(const PtE& p, bool need_t) {
     auto E = fe_norm(fe_sub(S, G));                   // (1,11)
     auto F = fe_norm(fe_sub(G, fe_norm(fe_dbl(ZZ)))); // (1,12)
     auto H = fe_norm(fe_sub(A, B));                   // (1,6)
-    r.X = fe_mul(E, F);
-    r.Y = fe_mul(G, H);
-    r.Z = fe_mul(F, G);
+    r.X = fe_mul<CHAIN>(E, F);
+    r.Y = fe_mul<CHAIN>(G, H);
+    r.Z = fe_mul<CHAIN>(F, G);
     r.T = fe_zero();
-    if (need_t) r.T = fe_mul(E, H);
+    if (need_t) r.T = fe_mul<CHAIN>(E, H);
   } else {
     auto E = fe_norm(fe_sub(fe_add(A, B), S));          // A + B - S            (1,8)
     auto aA = C::mul_aneg(A);                           // -a*A
     auto H = fe_add(aA, B);                             // -a*A + B             (<=6,12)
     auto G = fe_norm(fe_sub(aA, B));                    // -a*A - B             (1,14)
     auto F = fe_add(G, fe_dbl(ZZ));                     // G + 2Z^2             (3,18)
-    r.X = fe_mul(E, F);
-    r.Y = fe_mul(G, H);
-    r.Z = fe_mul(F, G);
+    r.X = fe_mul<CHAIN>(E, F);
+    r.Y = fe_mul<CHAIN>(G, H);
+    r.Z = fe_mul<CHAIN>(F, G);
     r.T = fe_zero();
-    if (need_t) r.T = fe_mul(E, H);
+    if (need_t) r.T = fe_mul<CHAIN>(E, H);
   }
   return r;
 }
 
-// H = B - a*A of the addition laws: B + ANEG*A, or B - A for a = 1
-template <class C, int L1, int V1, int L2, int V2>
-VRF_HD auto te_b_minus_aa(const Fe<L1, V1>& B, const Fe<L2, V2>& A) {
-  if constexpr (C::A_PLUS_ONE) return fe_norm(fe_sub(B, A));
-  else return fe_norm(fe_add(B, C::mul_aneg(A)));
+// H = Y1 Y2 - a X1 X2 of the addition laws as ONE fused sum of two products (fe_mul2: one reduction), like
+// E = X1 Y2 + Y1 X2, where add-2008-hwcd spends three reduced products A, B, S, three lazy additions, a subtraction and
+// two weak normalisations.  x2 is the second operand's x as stored, neg the sign the caller wants for that operand.
+//   a = -ANEG (Bandersnatch -5, JubJub / Ed25519 -1): H = Y1 Y2 + (ANEG X1) (+/-x2), ANEG X1 weakly normalised
+//   a = +1 (Baby-JubJub):                             H = Y1 Y2 + X1 (-/+x2)
+template <class C, bool CHAIN, int LX, int VX, int LY, int VY>
+VRF_HD auto te_add_h(const FeP& X1, const FeP& Y1, const Fe<LX, VX>& x2, bool neg, const Fe<LY, VY>& Y2) {
+  if constexpr (C::A_PLUS_ONE) return fe_mul2<CHAIN>(Y1, Y2, X1, fe_cneg(!neg, x2));
+  else if constexpr (C::ANEG == 1) return fe_mul2<CHAIN>(Y1, Y2, X1, fe_cneg(neg, x2));
+  else return fe_mul2<CHAIN>(Y1, Y2, fe_norm(C::mul_aneg(X1)), fe_cneg(neg, x2));          // ANEG X1: (1, 5 ANEG)
 }
 
 // a x^2 + y^2 - 1 from x^2, y^2: the left side of the curve equation a x^2 + y^2 - 1 = d x^2 y^2 (on-curve tests)
@@ -190,25 +198,22 @@ VRF_HD Fe<L + 1, (V > bias_k(V) ? V : bias_k(V))> fe_cneg(bool neg, const Fe<L, 
 // P + (+/-)Q with Q a cached entry (projective).  Unified: also correct for P == Q and for
 // either operand being the identity.  need_t = false skips the T coordinate (legal when the next
 // operation is a doubling or the result is only read as X, Y, Z); wave-uniform at every call site.
-template <class C>
+template <class C, bool CHAIN = false>
 VRF_HD PtE te_add_cached(const PtE& p, const PtC& q, bool neg, bool need_t = true) {
   auto X2 = fe_cneg(neg, q.X);                        // (2,8)
   auto dT2 = fe_cneg(neg, q.dT);                      // (2,4)
-  auto A = fe_mul(p.X, X2);                           // (1,2)
-  auto B = fe_mul(p.Y, q.Y);                          // (1,2)
-  auto Cc = fe_mul(p.T, dT2);                         // (1,2)
-  auto D = fe_mul(p.Z, q.Z);                          // (1,2)
-  auto S = fe_mul(fe_add(p.X, p.Y), fe_add(X2, q.Y)); // (2,10)x(3,13) -> (1,3)
-  auto E = fe_norm(fe_sub(S, fe_add(A, B)));          // (1,11)
+  auto Cc = fe_mul<CHAIN>(p.T, dT2);                         // (1,2)
+  auto D = fe_mul<CHAIN>(p.Z, q.Z);                          // (1,2)
+  auto E = fe_mul2<CHAIN>(p.X, q.Y, p.Y, X2);                // X1 Y2 + Y1 X2: L 1 + 2, V 25 + 40 -> (1,2)
+  auto H = te_add_h<C, CHAIN>(p.X, p.Y, q.X, neg, q.Y);   // Y1 Y2 - a X1 X2: a = -5: L 1 + 2, V 25 + 200 -> (1,5); a = -+1: (1,2)
   auto F = fe_sub(D, Cc);                             // (3,6)
   auto G = fe_add(D, Cc);                             // (2,4)
-  auto H = te_b_minus_aa<C>(B, A);                    // B - a*A              (1,12)
   PtE r;
-  r.X = fe_mul(E, F);
-  r.Y = fe_mul(G, H);
-  r.Z = fe_mul(F, G);
+  r.X = fe_mul<CHAIN>(E, F);                                 // V 12 -> (1,2)
+  r.Y = fe_mul<CHAIN>(G, H);                                 // V <= 20 -> (1,2)
+  r.Z = fe_mul<CHAIN>(F, G);                                 // L 6, V 24 -> (1,2)
   r.T = fe_zero();
-  if (need_t) r.T = fe_mul(E, H);
+  if (need_t) r.T = fe_mul<CHAIN>(E, H);                     // V <= 10 -> (1,2)
   return r;
 }
 
@@ -231,23 +236,20 @@ VRF_HD PtA pta_identity() {
   return a;
 }
 
-template <class C>
+template <class C, bool CHAIN = false>
 VRF_HD PtE te_add_affine(const PtE& p, const PtA& q, bool neg) {
   auto X2 = fe_cneg(neg, q.x);                        // (2,4)
   auto dT2 = fe_cneg(neg, q.dt);                      // (2,4)
-  auto A = fe_mul(p.X, X2);
-  auto B = fe_mul(p.Y, q.y);
-  auto Cc = fe_mul(p.T, dT2);
-  auto S = fe_mul(fe_add(p.X, p.Y), fe_add(X2, q.y));
-  auto E = fe_norm(fe_sub(S, fe_add(A, B)));
+  auto Cc = fe_mul<CHAIN>(p.T, dT2);                         // (1,2)
+  auto E = fe_mul2<CHAIN>(p.X, q.y, p.Y, X2);                // X1 y2 + Y1 x2: L 1 + 2, V 10 + 20 -> (1,2)
+  auto H = te_add_h<C, CHAIN>(p.X, p.Y, q.x, neg, q.y);   // Y1 y2 - a X1 x2: a = -5: V 10 + 100 -> (1,3); a = -+1: (1,2)
   auto F = fe_sub(p.Z, Cc);                           // (3,9)
   auto G = fe_add(p.Z, Cc);                           // (2,7)
-  auto H = te_b_minus_aa<C>(B, A);
   PtE r;
-  r.X = fe_mul(E, F);
-  r.Y = fe_mul(G, H);
-  r.Z = fe_mul(F, G);
-  r.T = fe_mul(E, H);
+  r.X = fe_mul<CHAIN>(E, F);                                 // V 18 -> (1,2)
+  r.Y = fe_mul<CHAIN>(G, H);                                 // V <= 21 -> (1,2)
+  r.Z = fe_mul<CHAIN>(F, G);                                 // L 6, V 63 -> (1,2)
+  r.T = fe_mul<CHAIN>(E, H);                                 // V <= 6 -> (1,2)
   return r;
 }
 

@@ -258,7 +258,8 @@ VRF_HD void sel8(uint32_t out[8], bool c, const uint32_t a[8], const uint32_t b[
 // reca / recb are recoded scalars (scalar_recode_signed4).  One te_dbl and one te_add call
 // site: the loop body is the whole hot path of IETF verification.
 // topB: the highest window of B's scalar that can be non-zero (challenge_top_window below; 63 = all of them).
-template <class C>
+// CHAIN: the ladder's products as single multiply-add chains (fe.cuh: mac); the verification ladders set it.
+template <class C, bool CHAIN = false>
 VRF_HD PtE straus2(const uint32_t* tabA, const uint32_t reca[8], const uint32_t* tabB,
                    const uint32_t recb[8], bool negB, int topB = 63) {
   PtE acc = te_identity();
@@ -266,7 +267,7 @@ VRF_HD PtE straus2(const uint32_t* tabA, const uint32_t reca[8], const uint32_t*
   for (int w = 63; w >= 0; --w) {
     if (w != 63) {
 #pragma unroll 1
-      for (int j = 0; j < 4; ++j) acc = te_dbl<C>(acc, j == 3);
+      for (int j = 0; j < 4; ++j) acc = te_dbl<C, CHAIN>(acc, j == 3);
     }
     const int terms = w <= topB ? 2 : 1;
 #pragma unroll 1
@@ -275,7 +276,7 @@ VRF_HD PtE straus2(const uint32_t* tabA, const uint32_t reca[8], const uint32_t*
       sel8(rec, t != 0, recb, reca);
       const uint32_t* tab = t ? tabB : tabA;
       int d = scalar_digit4(rec, w);
-      acc = te_add_cached<C>(acc, win_lookup(tab, d), (d < 0) != (t != 0 && negB), t + 1 < terms || w == 0);
+      acc = te_add_cached<C, CHAIN>(acc, win_lookup(tab, d), (d < 0) != (t != 0 && negB), t + 1 < terms || w == 0);
     }
   }
   return acc;
@@ -295,14 +296,14 @@ struct Straus4 {
   uint32_t rec[4][4];
   bool neg[4];
 };
-template <class C, int NT = 4, bool CT = false>
+template <class C, int NT = 4, bool CT = false, bool CHAIN = false>
 VRF_HD PtE straus4(const Straus4& q) {
   PtE acc = te_identity();
 #pragma unroll 1
   for (int w = 31; w >= 0; --w) {
     if (w != 31) {
 #pragma unroll 1
-      for (int j = 0; j < 4; ++j) acc = te_dbl<C>(acc, j == 3);
+      for (int j = 0; j < 4; ++j) acc = te_dbl<C, CHAIN>(acc, j == 3);
     }
 #pragma unroll 1
     for (int t = 0; t < NT; ++t) {
@@ -313,24 +314,24 @@ VRF_HD PtE straus4(const Straus4& q) {
       const uint32_t* tab = t == 0 ? q.tab[0] : t == 1 ? q.tab[1] : t == 2 ? q.tab[2] : q.tab[3];
       bool neg = t == 0 ? q.neg[0] : t == 1 ? q.neg[1] : t == 2 ? q.neg[2] : q.neg[3];
       int d = scalar_digit4_128(rec, w);
-      acc = te_add_cached<C>(acc, win_lookup_t<CT>(tab, d), (d < 0) != neg, t != NT - 1 || w == 0);   // doublings follow
+      acc = te_add_cached<C, CHAIN>(acc, win_lookup_t<CT>(tab, d), (d < 0) != neg, t != NT - 1 || w == 0);   // doublings follow
     }
   }
   return acc;
 }
 
 // k*P for one window table (prove: Gamma = sk*H, kH)
-template <class C, bool CT = false>
+template <class C, bool CT = false, bool CHAIN = false>
 VRF_HD PtE win_mul(const uint32_t* tab, const uint32_t rec[8], bool negate = false, int top = 63) {
   PtE acc = te_identity();
 #pragma unroll 1
   for (int w = top; w >= 0; --w) {
     if (w != top) {
 #pragma unroll 1
-      for (int j = 0; j < 4; ++j) acc = te_dbl<C>(acc, j == 3);
+      for (int j = 0; j < 4; ++j) acc = te_dbl<C, CHAIN>(acc, j == 3);
     }
     int d = scalar_digit4(rec, w);
-    acc = te_add_cached<C>(acc, win_lookup_t<CT>(tab, d), (d < 0) != negate, w == 0);
+    acc = te_add_cached<C, CHAIN>(acc, win_lookup_t<CT>(tab, d), (d < 0) != negate, w == 0);
   }
   return acc;
 }
@@ -502,8 +503,8 @@ VRF_HD PtA gcomb_entry(const uint32_t* tab, int w, int d) {
   e.dt = fe_select(z, id.dt, e.dt);
   return e;
 }
-// acc +/- k*Base
-template <class C>
+// acc +/- k*Base.  CHAIN as in straus2 below: set where the additions follow a verification ladder in the same kernel.
+template <class C, bool CHAIN = false>
 VRF_HD PtE gcomb_add(PtE acc, const uint32_t* tab, const uint32_t k[8], bool neg = false) {
   uint32_t carry = 0;
   int d = gcomb_digit(k, 0, carry);
@@ -516,7 +517,7 @@ VRF_HD PtE gcomb_add(PtE acc, const uint32_t* tab, const uint32_t k[8], bool neg
       d = gcomb_digit(k, w + 1, carry);
       e = gcomb_entry(tab, w + 1, d);
     }
-    acc = te_add_affine<C>(acc, cur, sgn != neg);
+    acc = te_add_affine<C, CHAIN>(acc, cur, sgn != neg);
   }
   return acc;
 }
@@ -983,10 +984,10 @@ VRF_HD void verify_straus_item(uint32_t* out_uv, const DevTables& T, const uint3
     scalar_recode_signed4(recc, c);
     PtE r;
     if (HALF == 0) {
-      r = win_mul<S>(tabs, recc, true, challenge_top_window(T.sq.str));
-      r = gcomb_add<S>(r, T.g_comb, s);
+      r = win_mul<S, false, true>(tabs, recc, true, challenge_top_window(T.sq.str));
+      r = gcomb_add<S, true>(r, T.g_comb, s);
     } else {
-      r = straus2<S>(tabs + 2 * WIN_TABLE_WORDS, recs, tabs + 4 * WIN_TABLE_WORDS, recc, true, challenge_top_window(T.sq.str));
+      r = straus2<S, true>(tabs + 2 * WIN_TABLE_WORDS, recs, tabs + 4 * WIN_TABLE_WORDS, recc, true, challenge_top_window(T.sq.str));
     }
     fe_store(out_uv, r.X);
     fe_store(out_uv + NL, r.Y);
@@ -1008,8 +1009,8 @@ VRF_HD void verify_straus_item(uint32_t* out_uv, const DevTables& T, const uint3
 #pragma unroll
     for (int i = 0; i < 4; ++i) { q.rec[2][i] = 0; q.rec[3][i] = 0; }
     q.neg[2] = false; q.neg[3] = false;
-    r = straus4<S, 2>(q);
-    r = gcomb_add<S>(r, T.g_comb, s);
+    r = straus4<S, 2, false, true>(q);
+    r = gcomb_add<S, true>(r, T.g_comb, s);
   } else {
     glv_decompose_bs(h[2], h[3], s);
 #pragma unroll
@@ -1019,7 +1020,7 @@ VRF_HD void verify_straus_item(uint32_t* out_uv, const DevTables& T, const uint3
     }
     q.tab[0] = tabs + 4 * WIN_TABLE_WORDS; q.tab[1] = tabs + 5 * WIN_TABLE_WORDS;
     q.tab[2] = tabs + 2 * WIN_TABLE_WORDS; q.tab[3] = tabs + 3 * WIN_TABLE_WORDS;
-    r = straus4<S, 4>(q);
+    r = straus4<S, 4, false, true>(q);
   }
   fe_store(out_uv, r.X);
   fe_store(out_uv + NL, r.Y);
