@@ -723,6 +723,59 @@ class Context:
                                                          dp(shared_scalars), dp(out), out_stride, dp(status), st),
                    "vrfhip_g1_lincomb_batch_dev")
 
+    @staticmethod
+    def _kzg_host_args(commitments, points, values, proofs, vk):
+        c = np.ascontiguousarray(commitments, dtype=np.uint8).reshape(-1, 48)
+        z = np.ascontiguousarray(points, dtype=np.uint8).reshape(-1, 32)
+        v = np.ascontiguousarray(values, dtype=np.uint8).reshape(-1, 32)
+        pi = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, 48)
+        k = _np_u8(vk, 480)
+        n = c.shape[0]
+        if z.shape[0] != n or v.shape[0] != n or pi.shape[0] != n:
+            raise ValueError("ragged batch")
+        return n, c, z, v, pi, k
+
+    def kzg_check_batch(self, commitments, points, values, proofs, vk) -> np.ndarray:
+        """KZG openings per item (`KZG10::check`): commitments / proofs (n, 48) compressed G1, points / values (n, 32)
+        little-endian < r, vk = g (96) || h (192) || beta_h (192).  -> status (n,): 0 / 1 / 2."""
+        n, c, z, v, pi, k = self._kzg_host_args(commitments, points, values, proofs, vk)
+        st = np.empty(n, dtype=np.uint8)
+        p = lambda a: _ptr(a) if n else None
+        _lib.check(self._lib.vrfhip_kzg_check_batch(self._h, n, p(c), p(z), p(v), p(pi), _ptr(k), p(st)), "vrfhip_kzg_check_batch")
+        return st
+
+    def kzg_check_batch_dev(self, commitments, points, values, proofs, vk, status, stream=None):
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _lib.check(self._lib.vrfhip_kzg_check_batch_dev(self._h, status.shape[0], commitments.data_ptr(), points.data_ptr(),
+                                                        values.data_ptr(), proofs.data_ptr(), vk.data_ptr(), status.data_ptr(),
+                                                        st), "vrfhip_kzg_check_batch_dev")
+
+    def kzg_check_batch_rlc(self, commitments, points, values, proofs, vk, seed: Optional[bytes] = None):
+        """The same n openings as ONE equation (`KZG10::batch_check`): three G1 MSMs + one pairing; a failing batch is
+        re-checked per item.  -> (status, batch_ok)"""
+        import os as _os
+        n, c, z, v, pi, k = self._kzg_host_args(commitments, points, values, proofs, vk)
+        sd = _np_u8(seed if seed is not None else _os.urandom(32), 32)
+        st = np.empty(n, dtype=np.uint8)
+        okf = ctypes.c_int32(1)
+        p = lambda a: _ptr(a) if n else None
+        _lib.check(self._lib.vrfhip_kzg_check_batch_rlc(self._h, n, p(c), p(z), p(v), p(pi), _ptr(k), _ptr(sd), p(st),
+                                                        ctypes.byref(okf)), "vrfhip_kzg_check_batch_rlc")
+        return st, bool(okf.value)
+
+    def kzg_check_batch_rlc_dev(self, commitments, points, values, proofs, vk, status, verdict, seed: bytes, sums=None,
+                                stream=None):
+        """Device form: status (n,) gets 0 / 2, verdict (1,) 0 / 1 / 2; sums (192,), optional, receives S_A || S_B."""
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        sd = _np_u8(seed, 32)
+        _lib.check(self._lib.vrfhip_kzg_check_batch_rlc_dev(self._h, status.shape[0], commitments.data_ptr(), points.data_ptr(),
+                                                            values.data_ptr(), proofs.data_ptr(), vk.data_ptr(), _ptr(sd),
+                                                            status.data_ptr(), verdict.data_ptr(),
+                                                            None if sums is None else sums.data_ptr(), st),
+                   "vrfhip_kzg_check_batch_rlc_dev")
+
     def hash_to_curve_batch(self, msgs) -> np.ndarray:
         if isinstance(msgs, np.ndarray):
             m = np.ascontiguousarray(msgs, dtype=np.uint8)

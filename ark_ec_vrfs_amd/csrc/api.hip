@@ -2089,6 +2089,195 @@ int32_t vrfhip_g1_lincomb_batch(vrfhip_ctx* ctx, size_t n, uint32_t k, const uin
   return VRFHIP_SUCCESS;
 }
 
+// ------------------------------------------------------------------------- KZG openings (k_kzg.hip)
+}  // extern "C"
+
+namespace {
+constexpr size_t KZG_VK_BYTES = 480;      // g (96) || h (192) || beta_h (192): the pairing calls' shared pair starts at byte 96
+// the argument rules all four forms share; *empty: the call is done
+int32_t kzg_args(vrfhip_ctx* ctx, size_t n, const uint8_t* c, const uint8_t* z, const uint8_t* v, const uint8_t* pi,
+                 const uint8_t* vk, const uint8_t* status, bool* empty) {
+  *empty = n == 0;
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
+  if (n > (size_t(1) << 28)) return fail(VRFHIP_ERR_BAD_ARG, "batch too large");
+  if (n == 0) return VRFHIP_SUCCESS;
+  if (!c || !z || !v || !pi || !vk || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  return VRFHIP_SUCCESS;
+}
+// both points of every item of a chunk through the checked decode: commitments -> d_c, proofs -> d_p, statuses -> d_dec[0..2m)
+void kzg_decode(size_t m, const uint8_t* c48, const uint8_t* p48, uint8_t* d_c, uint8_t* d_p, uint8_t* d_dec, hipStream_t st) {
+  for_chunks(m, G1_CODEC_CHUNK, [&](size_t base, size_t cnt) -> int32_t {
+    launch_g1_decode(cnt, c48 + base * 48, true, d_c + base * 96, d_dec + base, st);
+    launch_g1_decode(cnt, p48 + base * 48, true, d_p + base * 96, d_dec + m + base, st);
+    return VRFHIP_SUCCESS;
+  });
+}
+// the host-pointer forms' staging: the four arrays, vk, statuses, verdict
+struct KzgStage {
+  uint8_t *c, *z, *v, *pi, *vk, *st, *verdict;
+  void take(Stage& sg, size_t n) {
+    c = sg.take(n * 48); z = sg.take(n * 32); v = sg.take(n * 32); pi = sg.take(n * 48);
+    vk = sg.take(KZG_VK_BYTES); st = sg.take(n); verdict = sg.take(1);
+  }
+};
+int32_t kzg_send(vrfhip_ctx* ctx, const KzgStage& d, size_t n, const uint8_t* c, const uint8_t* z, const uint8_t* v,
+                 const uint8_t* pi, const uint8_t* vk) {
+  HIP_TRY(hipMemcpyAsync(d.c, c, n * 48, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(d.z, z, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(d.v, v, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(d.pi, pi, n * 48, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(d.vk, vk, KZG_VK_BYTES, hipMemcpyHostToDevice, ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t vrfhip_kzg_check_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_commitments48, const uint8_t* d_points32,
+                                   const uint8_t* d_values32, const uint8_t* d_proofs48, const uint8_t* d_vk, uint8_t* d_status,
+                                   void* stream) {
+  bool empty;
+  int32_t rc = kzg_args(ctx, n, d_commitments48, d_points32, d_values32, d_proofs48, d_vk, d_status, &empty);
+  if (rc || empty) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // decode -> rows -> linear combination -> pairing, a launch group of at most KZG_ITEM_CHUNK items at a time through
+  // the workspace: decoded C | decoded pi | decode statuses | bases | scalars | shared scalars | pairing items
+  const size_t cap = std::min(n, KZG_ITEM_CHUNK);
+  Stage carve(nullptr);
+  auto layout = [&](Stage& sg, uint8_t** p) {
+    p[0] = sg.take(cap * 96); p[1] = sg.take(cap * 96); p[2] = sg.take(2 * cap);
+    p[3] = sg.take(cap * 192); p[4] = sg.take(cap * 64); p[5] = sg.take(cap * 32); p[6] = sg.take(cap * 192);
+  };
+  uint8_t* w[7];
+  layout(carve, w);
+  rc = ensure_msm_workspace(ctx, carve.off);
+  if (rc) return rc;
+  Stage sg(ctx->d_msm_ws);
+  layout(sg, w);
+  for_chunks(n, cap, [&](size_t base, size_t m) -> int32_t {
+    kzg_decode(m, d_commitments48 + base * 48, d_proofs48 + base * 48, w[0], w[1], w[2], st);
+    launch_kzg_item_rows(m, w[0], w[1], w[2], d_points32 + base * 32, d_values32 + base * 32, w[3], w[4], w[5], w[6], st);
+    launch_g1_lincomb(m, 2, w[3], w[4], 1, d_vk, w[5], w[6], 192, d_status + base, st);      // A_i -> the items' first half
+    launch_pairing_check2(m, w[6], d_vk + 96, 0, d_status + base, st, ctx->d_pair_prep, ctx->dbg_pairing_layout);
+    return VRFHIP_SUCCESS;
+  });
+  HIP_TRY(hipGetLastError());
+  return VRFHIP_SUCCESS;
+}
+
+int32_t vrfhip_kzg_check_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* commitments48, const uint8_t* points32,
+                               const uint8_t* values32, const uint8_t* proofs48, const uint8_t* vk, uint8_t* status) {
+  bool empty;
+  int32_t rc = kzg_args(ctx, n, commitments48, points32, values32, proofs48, vk, status, &empty);
+  if (rc || empty) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  KzgStage d;
+  rc = stage_layout(ctx, [&](Stage& sg) { d.take(sg, n); });
+  if (rc) return rc;
+  if ((rc = kzg_send(ctx, d, n, commitments48, points32, values32, proofs48, vk))) return rc;
+  rc = vrfhip_kzg_check_batch_dev(ctx, n, d.c, d.z, d.v, d.pi, d.vk, d.st, ctx->stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(status, d.st, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+
+int32_t vrfhip_kzg_check_batch_rlc_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_commitments48, const uint8_t* d_points32,
+                                       const uint8_t* d_values32, const uint8_t* d_proofs48, const uint8_t* d_vk,
+                                       const uint8_t seed[32], uint8_t* d_status, uint8_t* d_verdict, uint8_t* d_sums,
+                                       void* stream) {
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
+  if (!d_verdict || !seed) return fail(VRFHIP_ERR_BAD_ARG, "NULL verdict or seed");
+  bool empty;
+  int32_t rc = kzg_args(ctx, n, d_commitments48, d_points32, d_values32, d_proofs48, d_vk, d_status, &empty);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipMemsetAsync(d_verdict, 0, 1, st));
+  if (empty) {                                    // the empty batch holds; its sums are the point at infinity twice
+    if (d_sums) HIP_TRY(hipMemsetAsync(d_sums, 0, 192, st));
+    return VRFHIP_SUCCESS;
+  }
+  // workspace: short layout (C_i, pi_i under r_i) | full layout (pi_i under r_i z_i, g) | digest tree | root | partial sums
+  // | the pairing item | decoded C | decoded pi | decode statuses
+  const int gs = g1_msm_groups(n, 2, G1_W_SHORT, ctx->cus), gf = g1_msm_groups(n + 1, 1, G1_W_FULL, ctx->cus);
+  uint8_t *w_short, *w_full, *d_digest_ws, *d_root, *d_part, *d_item, *d_c, *d_p, *d_dec;
+  auto layout = [&](Stage& sg) {
+    w_short = sg.take(g1_msm_workspace_bytes(n, 2, G1_W_SHORT, gs));
+    w_full = sg.take(g1_msm_workspace_bytes(n + 1, 1, G1_W_FULL, gf));
+    d_digest_ws = sg.take(digest_ws_bytes(n));
+    d_root = sg.take(32);
+    d_part = sg.take(kzg_partials(n) * KZG_PART_WORDS * sizeof(uint32_t));
+    d_item = sg.take(192);
+    d_c = sg.take(n * 96); d_p = sg.take(n * 96); d_dec = sg.take(2 * n);
+  };
+  Stage measure(nullptr);
+  layout(measure);
+  rc = ensure_msm_workspace(ctx, measure.off);
+  if (rc) return rc;
+  Stage sg(ctx->d_msm_ws);
+  layout(sg);
+  const G1MsmLayout S = g1_msm_layout(n, 2, G1_W_SHORT, gs, w_short), F = g1_msm_layout(n + 1, 1, G1_W_FULL, gf, w_full);
+  hipEvent_t* ev = prof_events(ctx);            // start | decode | prep (digest, prep, fold) | buckets | final, combine
+  if (ev) (void)hipEventRecord(ev[0], st);
+  kzg_decode(n, d_commitments48, d_proofs48, d_c, d_p, d_dec, st);
+  if (ev) (void)hipEventRecord(ev[1], st);
+  // the weights depend on every byte the caller handed over, as it arrived, and on the key: nothing a prover could
+  // influence is chosen after them (vrfhip_pairing_check_batch_rlc_dev)
+  DigestSrc ds{};
+  const uint8_t* arr[4] = {d_commitments48, d_points32, d_values32, d_proofs48};
+  const uint32_t width[4] = {48, 32, 32, 48};
+  for (int j = 0; j < 4; ++j) { ds.p[j] = arr[j]; ds.w[j] = width[j]; }
+  ds.n_arr = 4;
+  ds.ad = Blob{d_vk, nullptr, (uint32_t)KZG_VK_BYTES, true}.view(0);
+  launch_batch_digest(ds, n, 0, d_digest_ws, d_root, st);
+  launch_kzg_rlc(S, F, d_c, d_p, d_points32, d_values32, d_vk, seed, d_root, reinterpret_cast<uint32_t*>(d_part), d_status,
+                 d_item, st, ev ? ev + 2 : nullptr);
+  if (d_sums) HIP_TRY(hipMemcpyAsync(d_sums, d_item, 192, hipMemcpyDeviceToDevice, st));
+  // one pairing check for the whole batch, against the prepared lines of (h, beta_h); an invalid g left an all-0xFF item
+  launch_pairing_check2(1, d_item, d_vk + 96, 0, d_verdict, st, ctx->d_pair_prep, ctx->dbg_pairing_layout);
+  HIP_TRY(hipGetLastError());
+  return VRFHIP_SUCCESS;
+}
+
+int32_t vrfhip_kzg_check_batch_rlc(vrfhip_ctx* ctx, size_t n, const uint8_t* commitments48, const uint8_t* points32,
+                                   const uint8_t* values32, const uint8_t* proofs48, const uint8_t* vk, const uint8_t seed[32],
+                                   uint8_t* status, int32_t* batch_ok) {
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
+  if (!seed) return fail(VRFHIP_ERR_BAD_ARG, "seed is NULL");
+  if (batch_ok) *batch_ok = 1;
+  bool empty;
+  int32_t rc = kzg_args(ctx, n, commitments48, points32, values32, proofs48, vk, status, &empty);
+  if (rc || empty) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  KzgStage d;
+  rc = stage_layout(ctx, [&](Stage& sg) { d.take(sg, n); });
+  if (rc) return rc;
+  if ((rc = kzg_send(ctx, d, n, commitments48, points32, values32, proofs48, vk))) return rc;
+  rc = vrfhip_kzg_check_batch_rlc_dev(ctx, n, d.c, d.z, d.v, d.pi, d.vk, seed, d.st, d.verdict, nullptr, ctx->stream);
+  if (rc) return rc;
+  uint8_t verdict = 0;
+  HIP_TRY(hipMemcpyAsync(&verdict, d.verdict, 1, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (verdict != 0) {
+    // some opening is false (or the key is invalid): the per-item form names it
+    if (batch_ok) *batch_ok = 0;
+    rc = vrfhip_kzg_check_batch_dev(ctx, n, d.c, d.z, d.v, d.pi, d.vk, d.st, ctx->stream);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(status, d.st, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+
 // Test-only: quad-distributed Fp12 tower operations against the one-lane operations (k_pairing.hip)
 int32_t vrfhip_test_pairing_quad_ops(vrfhip_ctx* ctx, size_t n, const uint8_t* fp12_pairs, uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");

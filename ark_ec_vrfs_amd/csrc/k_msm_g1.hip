@@ -20,6 +20,7 @@
 #include "msm_g1.h"
 
 #include "g1.cuh"
+#include "g1_digits.cuh"
 #include "bls12_quad.cuh"     // qperm: DPP moves inside a quad (k_g1_final)
 #include "sha512.cuh"
 
@@ -27,32 +28,6 @@ namespace vrf {
 using namespace bls;
 
 static_assert(G1_PT_WORDS == G1P_WORDS && G1_AFF_WORDS == G1A_WORDS, "layout constants");
-
-// signed radix-2^10 digits of a little-endian integer k < 2^(10 W - 1); zero = every digit 0
-VRF_HD void g1_write_digits(int16_t* digits, size_t n, size_t i, int W, const uint32_t k[8], bool zero) {
-  uint32_t carry = 0;
-#pragma unroll 1
-  for (int w = 0; w < W; ++w) {
-    const int bit = w * G1_C, wi = bit >> 5, sh = bit & 31;
-    uint32_t lo = 0, hi = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (j == wi) lo = k[j];
-      if (j == wi + 1) hi = k[j];
-    }
-    uint32_t v = (sh ? ((lo >> sh) | (hi << (32 - sh))) : lo) & ((1u << G1_C) - 1);
-    v += carry;
-    int d = (int)v;
-    carry = 0;
-    if (v > (uint32_t)G1_BUCKETS) { d = (int)v - (1 << G1_C); carry = 1; }
-    digits[(size_t)w * n + i] = (int16_t)(zero ? 0 : d);
-  }
-}
-
-VRF_HD void g1_store_affine(uint32_t* dst, const G1Aff& P) {
-#pragma unroll
-  for (int j = 0; j < NLB; ++j) { dst[j] = (uint32_t)P.x.v[j]; dst[NLB + j] = (uint32_t)P.y.v[j]; }
-}
 
 // ------------------------------------------------------------------------------- prep
 struct Seed32 { uint8_t b[32]; };
@@ -370,7 +345,7 @@ G1MsmLayout g1_msm_layout(size_t n, int sets, int windows, int groups, void* ws)
   return L;
 }
 
-static void launch_core(const G1MsmLayout& L, hipStream_t st, hipEvent_t* ev) {
+void launch_g1_buckets(const G1MsmLayout& L, hipStream_t st) {
   const size_t lds_bytes = ((size_t)G1_BUCKETS * G1_PT_WORDS + 2 * G1_BUCKETS + 16) * 4;      // 90,176 B
   static bool attr_set = false;
   if (!attr_set) {
@@ -379,8 +354,14 @@ static void launch_core(const G1MsmLayout& L, hipStream_t st, hipEvent_t* ev) {
     attr_set = true;
   }
   hipLaunchKernelGGL(k_g1_buckets, dim3((unsigned)(L.sets * L.windows * L.groups)), dim3(G1_BLOCK), lds_bytes, st, L);
-  if (ev) (void)hipEventRecord(ev[1], st);
+}
+void launch_g1_final(const G1MsmLayout& L, hipStream_t st) {
   hipLaunchKernelGGL(k_g1_final, dim3((unsigned)L.sets), dim3(G1_FINAL_BLOCK), 0, st, L);
+}
+static void launch_core(const G1MsmLayout& L, hipStream_t st, hipEvent_t* ev) {
+  launch_g1_buckets(L, st);
+  if (ev) (void)hipEventRecord(ev[1], st);
+  launch_g1_final(L, st);
   if (ev) (void)hipEventRecord(ev[2], st);
 }
 

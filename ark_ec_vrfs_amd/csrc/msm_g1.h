@@ -46,6 +46,10 @@ void launch_g1_rlc(const G1MsmLayout& L, const uint8_t* g1, const uint8_t seed[3
 // `VariableBaseMSM::msm` on G1: bases n x 96 B, scalars n x 32 B little-endian (< r); result in L.sums[0..96],
 // status1[0] = 0 / 2 (a coordinate >= p, a point off the curve or a scalar >= r).  L: sets = 1, windows = 26.
 void launch_g1_msm(const G1MsmLayout& L, const uint8_t* bases, const uint8_t* scalars, uint8_t* status1, hipStream_t st);
+// The two kernels behind both calls above, for a prep kernel of another unit (k_kzg.hip): the bucket sums of every
+// (set, window, group) of a filled layout, then L.sums.
+void launch_g1_buckets(const G1MsmLayout& L, hipStream_t st);
+void launch_g1_final(const G1MsmLayout& L, hipStream_t st);
 
 // G1 codec (k_g1_codec.hip, g1_codec.cuh), one lane per point, no workspace; all arrays 4-byte aligned device memory.
 // points48: n x 48 B compressed (zcash / ark-bls12-381 form); g1_xy: n x 96 B affine as above; status[i] = 0 / 2.
@@ -63,5 +67,28 @@ constexpr int G1_LINCOMB_BLOCK = 128;                    // lanes per workgroup:
 void launch_g1_lincomb(size_t n, uint32_t k, const uint8_t* bases, const uint8_t* scalars, uint32_t m,
                        const uint8_t* shared_bases, const uint8_t* shared_scalars, uint8_t* out, size_t out_stride,
                        uint8_t* status, hipStream_t st);
+
+// KZG openings (k_kzg.hip, kzg.cuh).  g1c / g1p: the decoded commitments and proofs, n x 96 B (launch_g1_decode; an invalid
+// one is all-0xFF); z, v: n x 32 B little-endian; vk: g (96 B) || h || beta_h (192 B each).  All arrays 4-byte aligned.
+constexpr int KZG_BLOCK = 128;                           // items per workgroup of the prep kernel = one partial sum
+constexpr int KZG_PART_WORDS = 9;                        // one Fr partial sum (fe.cuh limbs)
+constexpr size_t KZG_ITEM_CHUNK = size_t(1) << 20;       // items per launch group of the per-item form
+// Per-item form: for every item the rows of launch_g1_lincomb(k = 2, m = 1, shared base g) whose result is
+// A_i = C_i - v_i g + z_i pi_i -- bases n x 192 B, scalars n x 64 B, shared_scalars n x 32 B -- and B_i = -pi_i at
+// items + i * 192 + 96.  dec_status: the 2n decode statuses (commitments, then proofs).  An item with an invalid point or
+// with z_i >= r or v_i >= r gets all-0xFF rows and B_i, so that it ends with status 2 in the lincomb and pairing launches.
+void launch_kzg_item_rows(size_t n, const uint8_t* g1c, const uint8_t* g1p, const uint8_t* dec_status, const uint8_t* z,
+                          const uint8_t* v, uint8_t* bases, uint8_t* scalars, uint8_t* shared_scalars, uint8_t* items,
+                          hipStream_t st);
+// Batched form: r_i = SHA-512("vrfhip-kzg-rlc-v1" || seed || d_root[32] || u64_le(i))[0..16]; fills S (sets = 2, windows =
+// G1_W_SHORT, n points: C_i and pi_i under r_i) and F (sets = 1, windows = G1_W_FULL, n + 1 points: pi_i under r_i z_i mod r
+// and g under -sum r_i v_i mod r), runs both multi-scalar multiplications and writes the one pairing item
+// S_A || S_B = (S.sums[0] + F.sums[0]) || -S.sums[1] to item192 (all-0xFF if g is invalid).  status[i] = 0 / 2.
+// partials: kzg_partials(n) * KZG_PART_WORDS words.  ev (nullable, 3 events): after prep + fold,
+// after the buckets of both layouts, after final + combine.
+inline size_t kzg_partials(size_t n) { return (n + KZG_BLOCK - 1) / KZG_BLOCK; }
+void launch_kzg_rlc(const G1MsmLayout& S, const G1MsmLayout& F, const uint8_t* g1c, const uint8_t* g1p, const uint8_t* z,
+                    const uint8_t* v, const uint8_t* vk, const uint8_t seed[32], const uint8_t* d_root, uint32_t* partials,
+                    uint8_t* status, uint8_t* item192, hipStream_t st, hipEvent_t* ev = nullptr);
 
 }  // namespace vrf

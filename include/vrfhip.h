@@ -575,6 +575,54 @@ int32_t vrfhip_g1_lincomb_batch_dev(vrfhip_ctx* ctx, size_t n, uint32_t k, const
                                     uint32_t m, const uint8_t* d_shared_bases, const uint8_t* d_shared_scalars, uint8_t* d_out,
                                     size_t out_stride, uint8_t* d_status, void* stream);
 
+/* KZG openings from wire bytes -- `KZG10::check` and `KZG10::batch_check` of ark-poly-commit for the plain single-point
+ * opening, the check that ends `ring::Verifier::verify` (src/lib.rs:14): item i = (C_i, z_i, v_i, pi_i) claims that the
+ * polynomial committed to by C_i takes the value v_i at z_i, and holds iff
+ *     e(C_i - v_i g + z_i pi_i, h) e(-pi_i, beta_h) = 1.
+ * commitments48, proofs48: n x 48 B in the compressed form vrfhip_g1_decode_batch reads, ALWAYS decoded with the checked
+ * semantics (on the curve and in the subgroup of order r): the 128-bit weights below are sound on subgroup points only, so
+ * there is no unchecked variant.  points32 (the z_i), values32 (the v_i): n x 32 B little-endian, < r.
+ * vk: 480 B = g (96 B, x || y little-endian as for vrfhip_g1_msm) || h (192 B) || beta_h (192 B, both in the G2 layout of
+ * vrfhip_pairing_check_batch) -- arkworks' `VerifierKey {g, h, beta_h}` as it is: the caller negates nothing, the library
+ * negates on the G1 side; g is a parameter because an SRS fixes its own.  `gamma_g` and hiding openings (`random_v`), and
+ * multi-point / multi-polynomial openings, are out of scope.  The Miller-loop lines of (h, beta_h) stay in the context as
+ * for the shared-pair calls above, so later calls with the same key reuse them.
+ * status[i]: 0 = the opening holds, 1 = VerificationFailure, 2 = InvalidData (a bad point encoding, a point outside the
+ * subgroup, z_i >= r or v_i >= r; an invalid vk makes every item InvalidData).  Infinity is a valid commitment and a valid
+ * proof: the zero polynomial opens as C = infinity, v = 0, pi = infinity, a constant one as C = v g, pi = infinity.
+ *
+ * vrfhip_kzg_check_batch*: per item -- decode, A_i = C_i + z_i pi_i + (r - v_i) g by vrfhip_g1_lincomb_batch's kernel,
+ * B_i = -pi_i, one pairing check per item against the shared pair.  The reference semantics and the fallback of:
+ * vrfhip_kzg_check_batch_rlc*: the batch as ONE equation.  With secret 128-bit weights
+ *     r_i = SHA-512("vrfhip-kzg-rlc-v1" || seed || D || u64_le(i))[0..16]   (little-endian)
+ * where D is the batch digest (vrfhip_test_batch_digest) over the four arrays as they arrive -- commitments48, points32,
+ * values32, proofs48, widths 48, 32, 32, 48 -- with the 480 bytes of vk as the leaves' common byte string, the weights go
+ * inside the sums:
+ *     S_A = sum r_i C_i + sum (r_i z_i mod r) pi_i - (sum r_i v_i mod r) g,   S_B = -sum r_i pi_i,
+ *     accept  <=>  e(S_A, h) e(S_B, beta_h) = 1:
+ * three G1 multi-scalar multiplications, one sum in Fr and one pairing, no per-item ladder.  `seed`: 32 bytes unpredictable
+ * to whoever made the items; a batch holding a false item passes with probability <= 2^-128.
+ * _dev form: d_status[i] = 0 (part of the batch) or 2 (InvalidData: left out of every sum); d_verdict[0] = 0 if the batch
+ * equation holds, 1 if it does not (vrfhip_kzg_check_batch_dev names the item), 2 if vk is invalid (a coordinate >= p, g, h
+ * or beta_h off its curve); d_sums (nullable): receives S_A || S_B, 192 B, the one pairing item (all-0xFF for an invalid g).
+ * Host form: the same per-item statuses as vrfhip_kzg_check_batch, since a failing batch is re-checked per item; *batch_ok
+ * (nullable) reports whether the single pairing sufficed.
+ * n <= 2^28; n = 0 reads and writes no array (the _rlc forms report an empty batch as holding: verdict 0, infinity twice in
+ * d_sums, *batch_ok = 1); device arrays 4-byte aligned; intermediates live in the context's MSM workspace.
+ * VRFHIP_ERR_UNSUPPORTED on a secp256r1 context, VRFHIP_ERR_BAD_ARG for a NULL array with n > 0, a NULL seed or verdict. */
+int32_t vrfhip_kzg_check_batch(vrfhip_ctx* ctx, size_t n, const uint8_t* commitments48, const uint8_t* points32,
+                               const uint8_t* values32, const uint8_t* proofs48, const uint8_t* vk, uint8_t* status);
+int32_t vrfhip_kzg_check_batch_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_commitments48, const uint8_t* d_points32,
+                                   const uint8_t* d_values32, const uint8_t* d_proofs48, const uint8_t* d_vk, uint8_t* d_status,
+                                   void* stream);
+int32_t vrfhip_kzg_check_batch_rlc(vrfhip_ctx* ctx, size_t n, const uint8_t* commitments48, const uint8_t* points32,
+                                   const uint8_t* values32, const uint8_t* proofs48, const uint8_t* vk, const uint8_t seed[32],
+                                   uint8_t* status, int32_t* batch_ok);
+int32_t vrfhip_kzg_check_batch_rlc_dev(vrfhip_ctx* ctx, size_t n, const uint8_t* d_commitments48, const uint8_t* d_points32,
+                                       const uint8_t* d_values32, const uint8_t* d_proofs48, const uint8_t* d_vk,
+                                       const uint8_t seed[32], uint8_t* d_status, uint8_t* d_verdict, uint8_t* d_sums,
+                                       void* stream);
+
 /* Building blocks --------------------------------------------------------------------- */
 
 /* `Input::new(data)` = Suite::data_to_point = hash_to_curve_ell2_rfc_9380 (src/lib.rs:14-16):

@@ -616,5 +616,61 @@ std::vector<Result> verify_batch_sharded(const std::vector<const Context<S>*>& c
 }
 }  // namespace pedersen
 
+// KZG openings on BLS12-381 (`KZG10::check` / `KZG10::batch_check`): thin mirrors of vrfhip_kzg_check_batch*.  An opening is
+// (commitment, point z, value v, proof) on the wire; vk = g || h || beta_h (480 bytes).  Works on a context of any suite but
+// secp256r1.
+namespace kzg {
+struct Opening {
+  std::array<uint8_t, 48> commitment;
+  std::array<uint8_t, 32> point, value;
+  std::array<uint8_t, 48> proof;
+};
+using VerifierKey = std::array<uint8_t, 480>;
+namespace detail_kzg {
+inline void columns(const std::vector<Opening>& items, Bytes& c, Bytes& z, Bytes& v, Bytes& pi) {
+  const size_t n = items.size();
+  c.resize(48 * n + 1); z.resize(32 * n + 1); v.resize(32 * n + 1); pi.resize(48 * n + 1);
+  for (size_t i = 0; i < n; ++i) {
+    std::memcpy(c.data() + 48 * i, items[i].commitment.data(), 48);
+    std::memcpy(z.data() + 32 * i, items[i].point.data(), 32);
+    std::memcpy(v.data() + 32 * i, items[i].value.data(), 32);
+    std::memcpy(pi.data() + 48 * i, items[i].proof.data(), 48);
+  }
+}
+}  // namespace detail_kzg
+// n x `KZG10::check`, one pairing check per item
+template <class S>
+std::vector<Result> check_batch(const Context<S>& ctx, const std::vector<Opening>& items, const VerifierKey& vk) {
+  const size_t n = items.size();
+  Bytes c, z, v, pi, st(n + 1);
+  detail_kzg::columns(items, c, z, v, pi);
+  check(vrfhip_kzg_check_batch(ctx.handle(), n, c.data(), z.data(), v.data(), pi.data(), vk.data(), st.data()),
+        "vrfhip_kzg_check_batch");
+  std::vector<Result> r(n);
+  for (size_t i = 0; i < n; ++i) r[i] = result_of(st[i]);
+  return r;
+}
+// `KZG10::batch_check`: three multi-scalar multiplications and one pairing; a failing batch is re-checked per item, so the
+// results are those of check_batch.  *batch_ok (nullable): whether the single pairing sufficed.
+template <class S>
+std::vector<Result> check_batch_rlc(const Context<S>& ctx, const std::vector<Opening>& items, const VerifierKey& vk,
+                                    bool* batch_ok = nullptr) {
+  const size_t n = items.size();
+  Bytes c, z, v, pi, st(n + 1);
+  detail_kzg::columns(items, c, z, v, pi);
+  std::array<uint8_t, 32> seed;
+  std::random_device rd;                                   // must be unpredictable to the provers
+  for (auto& b : seed) b = (uint8_t)rd();
+  int32_t ok = 1;
+  check(vrfhip_kzg_check_batch_rlc(ctx.handle(), n, c.data(), z.data(), v.data(), pi.data(), vk.data(), seed.data(), st.data(),
+                                   &ok),
+        "vrfhip_kzg_check_batch_rlc");
+  if (batch_ok) *batch_ok = ok != 0;
+  std::vector<Result> r(n);
+  for (size_t i = 0; i < n; ++i) r[i] = result_of(st[i]);
+  return r;
+}
+}  // namespace kzg
+
 }  // namespace ark_vrf_hip
 #endif  // VRFHIP_HPP
