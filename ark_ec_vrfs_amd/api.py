@@ -848,6 +848,28 @@ class Context:
         _lib.check(self._lib.vrfhip_test_scalar_mul(self._h, n, _ptr(k), _ptr(p), _ptr(out), _ptr(st)), "vrfhip_test_scalar_mul")
         return out, st
 
+    def test_verify_uv(self, pk, inp, out, c, s, affine=False, keyset=None, key_index=None):
+        """U = s*G - c*pk and V = s*input - c*output as the verification kernels compute them, in the encoding the
+        challenge hash takes; (u, v, status).  keyset / key_index replace pk (the keyed launches)."""
+        pw = 64 if affine else self.point_bytes()
+        inp, out = (np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, pw) for x in (inp, out))
+        c, s = (np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 32) for x in (c, s))
+        n = inp.shape[0]
+        if keyset is None:
+            pk = np.ascontiguousarray(pk, dtype=np.uint8).reshape(-1, pw)
+            idx, rows = None, (pk, out, c, s)
+        else:
+            idx = np.ascontiguousarray(key_index, dtype=np.uint32).reshape(-1)
+            pk, rows = None, (idx, out, c, s)
+        if not all(x.shape[0] == n for x in rows):
+            raise ValueError("ragged batch")
+        u, v = (np.empty((n, self.point_bytes()), np.uint8) for _ in range(2))
+        st = np.empty(n, np.uint8)
+        _lib.check(self._lib.vrfhip_test_verify_uv(
+            self._h, n, 1 if affine else 0, _ptr(pk), None if keyset is None else keyset.handle, _ptr(idx), _ptr(inp),
+            _ptr(out), _ptr(c), _ptr(s), _ptr(u), _ptr(v), _ptr(st)), "vrfhip_test_verify_uv")
+        return u, v, st
+
     def _test_hash(self, fn, name, msgs, width):
         blob, off = _pack_var([bytes(m) for m in msgs])
         out = np.empty((len(msgs), width), np.uint8)

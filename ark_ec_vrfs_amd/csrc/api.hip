@@ -406,7 +406,7 @@ int32_t stage_blob(vrfhip_ctx* ctx, const StagedBlob& b, Blob* out) {
 
 extern "C" {
 
-int32_t vrfhip_abi_version(void) { return 144; }
+int32_t vrfhip_abi_version(void) { return 145; }
 
 const char* vrfhip_last_error(void) { return g_last_error.c_str(); }
 
@@ -798,7 +798,9 @@ int32_t vrfhip_ctx_profile_read(vrfhip_ctx* ctx, double stage_ms[4], uint64_t* l
 namespace {
 int32_t verify_dev_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* d_pk, const uint8_t* d_input,
                         const uint8_t* d_output, const uint8_t* d_c, const uint8_t* d_s, const Blob& ad, uint8_t* d_status,
-                        void* stream, const vrfhip_keyset* ks = nullptr, const uint32_t* d_key_index = nullptr) {
+                        void* stream, const vrfhip_keyset* ks = nullptr, const uint32_t* d_key_index = nullptr,
+                        uint8_t* d_u = nullptr, uint8_t* d_v = nullptr) {
+  // d_u, d_v (vrfhip_test_verify_uv; both or neither): the launchers end with their readout kernel instead of the finish stage
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (ks && (ks->ctx != ctx || !d_key_index)) return fail(VRFHIP_ERR_BAD_ARG, "key set of another context, or NULL key index");
   if (n == 0) return VRFHIP_SUCCESS;
@@ -821,6 +823,7 @@ int32_t verify_dev_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* d
       a.ad = ad.view(base);
       a.status = d_status + base;
       if (ks) { a.key_index = d_key_index + base; a.n_keys = ks->n_keys; a.key_valid = ks->d_valid; a.key_combs = ks->d_combs; }
+      if (d_u) { a.u_out = d_u + base * ctx->pt_bytes(); a.v_out = d_v + base * ctx->pt_bytes(); }
     };
     if (ctx->sw) {
       p256::VerifyArgs a{};
@@ -2582,6 +2585,38 @@ int32_t vrfhip_test_point_add(vrfhip_ctx* ctx, size_t n, const uint8_t* a, const
   FIELD_CALL(ctx, launch_test_point_add((int)ctx->suite, n, d_a, d_b, d_o, d_st, ctx->T, ctx->stream));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, d_o, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+
+// U and V of IETF verification out of the verifier's own launches: verify_dev_impl with the readout outputs set, so the
+// decode and ladder kernels and their launch shape are the ones vrfhip_ietf_verify_batch[_keyed / _affine] gets for this n.
+int32_t vrfhip_test_verify_uv(vrfhip_ctx* ctx, size_t n, int32_t affine, const uint8_t* pk, const vrfhip_keyset* keys,
+                              const uint32_t* key_index, const uint8_t* input, const uint8_t* output, const uint8_t* c,
+                              const uint8_t* s, uint8_t* u_out, uint8_t* v_out, uint8_t* status) {
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (n == 0) return VRFHIP_SUCCESS;
+  if (keys ? (!key_index || affine) : !pk) return fail(VRFHIP_ERR_BAD_ARG, "pk, or a key set with per-item indices and compressed points");
+  if (!input || !output || !c || !s || !u_out || !v_out || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  const size_t pw = affine ? 64 : ctx->pt_bytes(), ow = ctx->pt_bytes();
+  const uint8_t* src[6] = {keys ? nullptr : pk, input, output, c, s, reinterpret_cast<const uint8_t*>(keys ? key_index : nullptr)};
+  const size_t w[6] = {pw, pw, pw, 32, 32, 4};
+  uint8_t *d[6], *d_u, *d_v, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
+    for (int i = 0; i < 6; ++i) d[i] = sg.take(n * w[i]);
+    d_u = sg.take(n * ow); d_v = sg.take(n * ow); d_st = sg.take(n);
+  });
+  if (rc) return rc;
+  for (int i = 0; i < 6; ++i)
+    if (src[i]) HIP_TRY(hipMemcpyAsync(d[i], src[i], n * w[i], hipMemcpyHostToDevice, ctx->stream));
+  rc = verify_dev_impl(ctx, n, affine != 0, d[0], d[1], d[2], d[3], d[4], Blob{nullptr, nullptr, 0, true}, d_st, ctx->stream, keys,
+                       keys ? reinterpret_cast<const uint32_t*>(d[5]) : nullptr, d_u, d_v);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(u_out, d_u, n * ow, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(v_out, d_v, n * ow, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return VRFHIP_SUCCESS;

@@ -378,6 +378,30 @@ __global__ void __launch_bounds__(BLOCK, 2) k_bsw_verify_finish(VerifyArgs a) {
   a.status[i] = (uint8_t)(!valid ? ST_INVALID_DATA : (diff == 0 ? ST_OK : ST_VERIFICATION_FAILURE));
 }
 
+// vrfhip_test_verify_uv: U and V as the ladder kernels above left them, encoded as k_bsw_verify_finish encodes them for the
+// challenge hash (bsw_encode_frac, one shared inversion; the neutral element comes out as 32 zero bytes + the flag byte
+// 0x40).  status: 0 where the decode stage accepted the item's points and s < r, else 2 with zero bytes for u and v.
+__global__ void __launch_bounds__(BLOCK, 2) k_bsw_test_verify_uv_readout(VerifyArgs a) {
+  size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const uint32_t* pts = a.ws.pts + i * PROVE_PTS_WORDS;
+  SwFrac f[2];
+  FeN dens[2], inv[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    f[j] = bsw_frac<BswS>(fe_load<1, 5>(pts + j * UV_WORDS), fe_load<1, 5>(pts + j * UV_WORDS + NL),
+                          fe_load<1, 5>(pts + j * UV_WORDS + 2 * NL));
+    dens[j] = f[j].den;
+  }
+  fe_batch_inv(inv, dens);
+  uint32_t sc[8];
+  load32(sc, a.s, i);
+  const bool ok = a.ws.flags[i] != 0 && fr_is_canonical<BswS>(sc);
+  store33(a.u_out, i, bsw_encode_frac(f[0], inv[0]), ok);
+  store33(a.v_out, i, bsw_encode_frac(f[1], inv[1]), ok);
+  a.status[i] = ok ? ST_OK : ST_INVALID_DATA;
+}
+
 // ---- Pedersen verify, stage 1: decode H, Gamma, pk_com, R, Ok; tables of the first three; affine R, Ok; challenge ----
 // AFFINE (a.affine_in: 1 canonical, 2 Montgomery-256): the five points come as Weierstrass x || y (64 bytes): range and
 // curve checks instead of the square roots, the same ONE map inversion; the encodings come out canonical.  A separate
@@ -625,6 +649,10 @@ void launch_bsw_ietf_verify(const VerifyArgs& a, hipStream_t st, hipEvent_t* ev)
   if (a.key_index) hipLaunchKernelGGL(k_bsw_verify_comb_u, grid_for(a.n), dim3(BLOCK), 0, st, a);
   else hipLaunchKernelGGL(k_bsw_verify_straus<0>, grid_for(a.n), dim3(BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[3], st);
+  if (a.u_out) {                                  // vrfhip_test_verify_uv: U, V instead of the verdict
+    hipLaunchKernelGGL(k_bsw_test_verify_uv_readout, grid_for(a.n), dim3(BLOCK), 0, st, a);
+    return;
+  }
   hipLaunchKernelGGL(k_bsw_verify_finish, grid_for(a.n), dim3(BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[4], st);
 }

@@ -291,6 +291,32 @@ __global__ void __launch_bounds__(BLOCK) k_test_scalar_mul(size_t n, const uint8
   store32(out, i, e);
   status[i] = ok ? ST_OK : ST_INVALID_DATA;
 }
+// U and V of IETF verification as the ladder kernels of launch_ietf_verify left them in the workspace (projective X, Y, Z at
+// pts[i][0..1]): made affine with one inversion and encoded as the finish stage encodes them for the challenge hash
+// (verify_finish_multi: te_encode_affine with the suite's flags; the identity comes out as y = 1 with the sign bit clear).
+// status: 0 where the decode stage accepted the item's points and s < r, else 2 with zero bytes for u and v.
+template <class S>
+__global__ void __launch_bounds__(BLOCK) k_test_verify_uv_readout(VerifyArgs a) {
+  size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const uint32_t* uv = a.ws.pts + i * PROVE_PTS_WORDS;
+  FeP zin[2] = {fe_load<1, 5>(uv + 2 * NL), fe_load<1, 5>(uv + UV_WORDS + 2 * NL)};
+  FeN zi[2];
+  fe_batch_inv(zi, zin);
+  uint32_t s[8], e[2][8];
+  load32(s, a.s, i);
+  const bool ok = a.ws.flags[i] != 0 && fr_is_canonical<S>(s);
+  te_encode_affine(e[0], fe_mul(fe_load<1, 5>(uv), zi[0]), fe_mul(fe_load<1, 5>(uv + NL), zi[0]), a.T.sq.str.flags);
+  te_encode_affine(e[1], fe_mul(fe_load<1, 5>(uv + UV_WORDS), zi[1]), fe_mul(fe_load<1, 5>(uv + UV_WORDS + NL), zi[1]),
+                   a.T.sq.str.flags);
+  if (!ok) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { e[0][j] = 0; e[1][j] = 0; }
+  }
+  store32(a.u_out, i, e[0]);
+  store32(a.v_out, i, e[1]);
+  a.status[i] = ok ? ST_OK : ST_INVALID_DATA;
+}
 // which = 0: SHA-512 (64 B per item); which = 1: expand_message_xmd to 96 bytes with the context's DST
 template <class S>
 __global__ void __launch_bounds__(BLOCK) k_test_hash(size_t n, BytesView msg, uint8_t* out, int which, SuiteStr ss) {
@@ -325,6 +351,9 @@ void launch_test_point_add(int suite, size_t n, const uint8_t* a, const uint8_t*
 void launch_test_scalar_mul(int suite, size_t n, const uint8_t* k, const uint8_t* p, uint8_t* out, uint8_t* status,
                             uint32_t* tabs, DevTables T, hipStream_t st) {
   if (n) VRF_DISPATCH_SUITE(suite, hipLaunchKernelGGL(k_test_scalar_mul<S>, grid_for(n), dim3(BLOCK), 0, st, n, k, p, out, status, tabs, T));
+}
+void launch_test_verify_uv_readout(const VerifyArgs& a, hipStream_t st) {
+  if (a.n) VRF_DISPATCH_SUITE(a.suite, hipLaunchKernelGGL(k_test_verify_uv_readout<S>, grid_for(a.n), dim3(BLOCK), 0, st, a));
 }
 void launch_test_hash(int suite, size_t n, BytesView msg, uint8_t* out, int which, DevTables T, hipStream_t st) {
   if (n) VRF_DISPATCH_SUITE(suite, hipLaunchKernelGGL(k_test_hash<S>, grid_for(n), dim3(BLOCK), 0, st, n, msg, out, which, T.sq.str));

@@ -206,6 +206,31 @@ __global__ void __launch_bounds__(P256_BLOCK) k_p256_verify_finish(p256::VerifyA
   a.status[i] = p256_verify_finish_item(U, V, enc, c, ad, ad_len, a.str);
 }
 
+// vrfhip_test_verify_uv: U and V as k_p256_verify_mul left them, through the routine the finish stage hashes them with
+// (sw_to_sec1, one shared inversion) and the Sec1 writer.  The point at infinity, which the challenge hash absorbs as the
+// single byte 0x00, is written as 0x00 followed by 32 zero bytes.  status: 0 where the decode stage accepted the item
+// (points on the curve, s < n), else 2 with zero bytes for u and v (the ladders skip such an item).
+__global__ void __launch_bounds__(P256_BLOCK) k_p256_test_verify_uv_readout(p256::VerifyArgs a) {
+  const size_t i = (size_t)blockIdx.x * P256_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  const size_t cap = a.ws.cap;
+  const bool ok = a.ws.flags[i] != 0;
+  Sec1W w[2] = {};
+  if (ok) {
+    const PtW uv[2] = {ptw_load(ws_pt(a.ws.pts, cap, i, 0), cap), ptw_load(ws_pt(a.ws.pts, cap, i, 1), cap)};
+    sw_to_sec1<false>(w, uv);
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const bool zero = !ok || w[j].tag == 0u;
+    uint32_t xw[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) xw[k] = zero ? 0u : w[j].xw[k];
+    sec1_store((j == 0 ? a.u_out : a.v_out) + i * SEC1_LEN, zero ? 0u : w[j].tag, xw);
+  }
+  a.status[i] = ok ? 0 : 2;
+}
+
 // ------------------------------------------------------------------------------------------------ IETF prove
 // Stage 0: every item's first counter whose candidate decodes.  The lanes of a persistent wave draw items from a global
 // queue: a lane whose attempt succeeded records the counter and takes the next item at once, so a wave performs about
@@ -549,6 +574,10 @@ void launch_verify(const VerifyArgs& a, hipStream_t st, hipEvent_t* ev) {
   if (ev) (void)hipEventRecord(ev[2], st);
   hipLaunchKernelGGL(k_p256_verify_mul<0>, dim3(g), dim3(P256_BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[3], st);
+  if (a.u_out) {                                  // vrfhip_test_verify_uv: U, V instead of the verdict
+    hipLaunchKernelGGL(k_p256_test_verify_uv_readout, dim3(g), dim3(P256_BLOCK), 0, st, a);
+    return;
+  }
   hipLaunchKernelGGL(k_p256_verify_finish, dim3(g), dim3(P256_BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[4], st);
 }

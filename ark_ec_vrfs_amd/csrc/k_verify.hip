@@ -155,6 +155,7 @@ static void launch_verify_t(const VerifyArgs& a, hipStream_t st, hipEvent_t* ev)
     dim3 g2 = grid_for(a.n);
     g2.y = 2;
     hipLaunchKernelGGL(k_verify_straus_both<S>, g2, dim3(BLOCK), 0, st, a);
+    if (a.u_out) { launch_test_verify_uv_readout(a, st); return; }
     VRF_LAUNCH_MINW(k_verify_finish, S, lanes_k_, gk, spread_lds_bytes(gk.x), st, a);
     return;
   }
@@ -164,6 +165,7 @@ static void launch_verify_t(const VerifyArgs& a, hipStream_t st, hipEvent_t* ev)
   if (a.key_index) hipLaunchKernelGGL(k_verify_comb_u<S>, grid_for(a.n), dim3(BLOCK), 0, st, a);
   else hipLaunchKernelGGL((k_verify_straus<S, 0>), grid_for(a.n), dim3(BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[3], st);
+  if (a.u_out) { launch_test_verify_uv_readout(a, st); return; }      // vrfhip_test_verify_uv: U, V instead of the verdict
   VRF_LAUNCH_MINW(k_verify_finish, S, lanes_k_, gk, spread_lds_bytes(gk.x), st, a);
   if (ev) (void)hipEventRecord(ev[4], st);
 }

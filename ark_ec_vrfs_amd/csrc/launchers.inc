@@ -32,6 +32,9 @@ void launch_test_point_add(int suite, size_t n, const uint8_t* a, const uint8_t*
                            DevTables T, hipStream_t st);
 void launch_test_scalar_mul(int suite, size_t n, const uint8_t* k, const uint8_t* p, uint8_t* out, uint8_t* status,
                             uint32_t* tabs, DevTables T, hipStream_t st);
+// the verifier's U and V as the ladders left them in a.ws.pts (launch_ietf_verify with a.u_out set runs this in place of its
+// finish stage): one inversion, te_encode_affine with the suite's flags -> a.u_out, a.v_out, a.status
+void launch_test_verify_uv_readout(const VerifyArgs& a, hipStream_t st);
 void launch_test_hash(int suite, size_t n, BytesView msg, uint8_t* out, int which, DevTables T, hipStream_t st);
 // host copies of the field's square-root tables and the built-in descriptor points (constants*.gen.h), for the C ABI
 const uint32_t* field_sqrt_p(size_t* bytes);

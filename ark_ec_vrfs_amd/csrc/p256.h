@@ -54,6 +54,9 @@ struct VerifyArgs {
   const uint8_t* key_valid;          // [n_keys]
   const uint32_t* key_combs;         // [n_keys][key_rows][128][28] radix-256 comb rows 0 .. key_rows - 1 of every key
   int key_rows;                      // challenge_len + 1: the rows a challenge can reach
+  // vrfhip_test_verify_uv (u_out != nullptr): decode and ladders as ever, then k_p256_verify_uv_readout in place of the
+  // finish stage: U, V as n x 33 B Sec1 strings and status 0 / 2 per item.  ad is not read.
+  uint8_t *u_out, *v_out;
 };
 struct ProveArgs {
   size_t n;

@@ -92,6 +92,9 @@ struct VerifyArgs {
   size_t n_keys;
   Workspace ws;
   DevTables T;
+  // vrfhip_test_verify_uv (u_out != nullptr): the launcher runs its decode and ladder stages as for any batch and, in place
+  // of the finish stage, the readout kernel: enc(U), enc(V) (one wire point each) and status 0 / 2 per item.  ad is not read.
+  uint8_t *u_out, *v_out;
 };
 
 struct ProveArgs {

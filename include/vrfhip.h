@@ -745,6 +745,19 @@ int32_t vrfhip_test_point_add(vrfhip_ctx* ctx, size_t n, const uint8_t* a, const
                               uint8_t* status);
 int32_t vrfhip_test_scalar_mul(vrfhip_ctx* ctx, size_t n, const uint8_t* scalars, const uint8_t* points, uint8_t* out,
                                uint8_t* status);
+/* Test-only: the two points IETF verification hashes into its challenge, out of the verifier's own kernels.
+ *   U = s*G - c*pk, V = s*input - c*output   (`ietf::Verifier::verify`, src/lib.rs:14)
+ * The call runs the decode and ladder launches that vrfhip_ietf_verify_batch (affine != 0: _affine; keys != NULL: _keyed,
+ * pk is then not read and key_index[i] names item i's key) chooses for this n, and instead of the finish stage a readout
+ * of the projective results: one inversion, then the encoding the challenge hash takes -- 32-byte compressed points on
+ * the Edwards suites (the identity as y = 1, sign bit clear), 33-byte points on bandersnatch_sw (the point at infinity as
+ * 32 zero bytes + flag 0x40) and secp256r1 (Sec1; the point at infinity as 0x00 + 32 zero bytes).  c and s as the
+ * verify calls take them; a c of more than challenge_len bytes gets the ladder of its low windows (some other point).
+ * u_out, v_out: n x point bytes (host); status[i] = 0 where the three points decode (subgroup tests as the context's flags
+ * say; keyed: the index names a valid key) and s < r, else 2 with zero bytes in u_out and v_out. */
+int32_t vrfhip_test_verify_uv(vrfhip_ctx* ctx, size_t n, int32_t affine, const uint8_t* pk, const vrfhip_keyset* keys,
+                              const uint32_t* key_index, const uint8_t* input, const uint8_t* output, const uint8_t* c,
+                              const uint8_t* s, uint8_t* u_out, uint8_t* v_out, uint8_t* status);
 int32_t vrfhip_test_sha512(vrfhip_ctx* ctx, size_t n, const uint8_t* msg, const uint32_t* msg_off, uint32_t msg_len,
                            uint8_t* out);
 int32_t vrfhip_test_xmd(vrfhip_ctx* ctx, size_t n, const uint8_t* msg, const uint32_t* msg_off, uint32_t msg_len,

@@ -3,6 +3,7 @@
 // over 33-byte encodings and try-and-increment -- the functions k_bsw.hip composes.  Never linked into libvrfhip.so.
 #include "../../ark_ec_vrfs_amd/csrc/bsw_core.cuh"
 #include <cstring>
+#include <vector>
 using namespace vrf;
 namespace {
 SuiteStr make_str(const char* id, uint32_t challenge_len) {
@@ -54,6 +55,56 @@ void hb_decode_shared(const uint8_t* encs, int n, uint8_t* te_xy, uint8_t* flags
     out(te_xy + 64 * p, x); out(te_xy + 64 * p + 32, y);
     flags[p] = (uint8_t)(((st[p] & BSW_A_OK) ? 1 : 0) | ((st[p] & BSW_A_INF) ? 2 : 0));
   }
+}
+// The verifier's U = s*G - c*pk and V = s*H - c*Gamma as k_bsw.hip stages them: k_bsw_verify_decode's shared-inversion way
+// in with the subgroup tests of check_mask, bsw_load_cs, the Edwards suite's verify_straus_item, and the encoding of
+// k_bsw_test_verify_uv_readout (bsw_frac, one inversion, bsw_encode_frac).  0, or 2 with zero bytes in u and v.
+int hb_verify_uv(uint32_t challenge_len, uint32_t check_mask, const uint8_t* pk, const uint8_t* h, const uint8_t* g, const uint8_t* c,
+                 const uint8_t* s, uint8_t* u, uint8_t* v) {
+  static std::vector<uint32_t> g_comb;                     // the generator's fixed-base table, by the device's own builder
+  if (g_comb.empty()) {
+    g_comb.assign(GCOMB_WORDS, 0);
+    std::vector<uint32_t> prefix((size_t)GC_SEG * NL);
+    for (int w = 0; w < GC_ROWS; ++w)
+      for (int seg = 0; seg < GC_SEGS; ++seg) gcomb_build_segment<BswS>(g_comb.data(), prefix.data(), BswS::gx(), BswS::gy(), w, seg);
+  }
+  DevTables T{};
+  T.sq = tables();
+  T.sq.str.challenge_len = challenge_len;
+  T.g_comb = g_comb.data();
+  const uint8_t* src[3] = {pk, h, g};
+  std::vector<uint32_t> tabs(VERIFY_TABS * WIN_TABLE_WORDS), uv(2 * UV_WORDS);
+  uint32_t scr[3 * BSW_SLOT], st[3];
+  FeN run = fe_one();
+  for (int p = 0; p < 3; ++p) st[p] = bsw_in_a(scr + p * BSW_SLOT, run, load33(src[p], 0), T.sq);
+  FeN inv = fe_inv(run);
+  bool valid = true;
+  for (int p = 2; p >= 0; --p) {
+    FeN x, y;
+    bsw_in_b(x, y, inv, scr + p * BSW_SLOT, (st[p] & BSW_A_INF) != 0);
+    valid = valid && (st[p] & BSW_A_OK) != 0;
+    if ((check_mask >> p) & 1u) valid = in_prime_subgroup<BswS>(x, y, T.sq) && valid;
+    build_glv_tables<BswS>(tabs.data() + p * 2 * WIN_TABLE_WORDS, x, y);
+  }
+  uint32_t cw[8], cr[8], sw[8];
+  memcpy(cw, c, 32); memcpy(sw, s, 32);
+  fr_reduce256<BswS>(cr, cw);
+  const bool canon = fr_is_canonical<BswS>(sw);
+  for (int j = 0; j < 8; ++j) { cr[j] = canon ? cr[j] : 0; sw[j] = canon ? sw[j] : 0; }
+  verify_straus_item<BswS, 0>(uv.data(), T, tabs.data(), cr, sw);
+  verify_straus_item<BswS, 1>(uv.data() + UV_WORDS, T, tabs.data(), cr, sw);
+  valid = valid && canon;
+  SwFrac f[2];
+  FeN dens[2], di[2];
+  for (int j = 0; j < 2; ++j) {
+    const uint32_t* q = uv.data() + j * UV_WORDS;
+    f[j] = bsw_frac<BswS>(fe_load<1, 5>(q), fe_load<1, 5>(q + NL), fe_load<1, 5>(q + 2 * NL));
+    dens[j] = f[j].den;
+  }
+  fe_batch_inv(di, dens);
+  store33(u, 0, bsw_encode_frac(f[0], di[0]), valid);
+  store33(v, 0, bsw_encode_frac(f[1], di[1]), valid);
+  return valid ? 0 : 2;
 }
 void hb_canonical(const uint8_t* enc, uint8_t* o) { store33(o, 0, enc33_canonical(load33(enc, 0))); }
 void hb_challenge(const uint8_t* pts, const uint8_t* ad, uint32_t ad_len, uint8_t* c) {

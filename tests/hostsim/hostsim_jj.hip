@@ -33,6 +33,7 @@ struct HostTablesJ {
 };
 HostTablesJ& HJ() { static HostTablesJ h; h.t.sq.str = g_hj_str; return h; }
 }
+#include "verify_uv.inc"
 static uint32_t g_check_mask_jj = 0;   // CHK_* bits for the decode stages (0 = on-curve only)
 extern "C" {
 void hj_set_check_mask(uint32_t m) { g_check_mask_jj = m; }
@@ -102,6 +103,10 @@ uint32_t hj_ietf_verify(const uint8_t* pk, const uint8_t* h, const uint8_t* g, c
   verify_straus_item<SJ, 0>(uv.data(), HJ().t, tabs.data(), c2, s2);
   verify_straus_item<SJ, 1>(uv.data() + UV_WORDS, HJ().t, tabs.data(), c2, s2);
   return verify_finish_item<SJ>(uv.data(), w[0], w[1], w[2], w[3], w[4], valid, ad, ad_len, g_hj_str);
+}
+uint32_t hj_verify_uv(uint32_t challenge_len, const uint8_t* pk, const uint8_t* h, const uint8_t* g, const uint8_t* c,
+                      const uint8_t* s, uint8_t* u, uint8_t* v) {
+  return host_verify_uv<SJ>(HJ().t, challenge_len, g_check_mask_jj, pk, h, g, c, s, u, v);
 }
 uint32_t hj_pedersen_verify(const uint8_t* h, const uint8_t* g, const uint8_t* proof160, const uint8_t* ad, uint32_t ad_len) {
   uint32_t enc[5][8], s[8], sb[8], c[8];

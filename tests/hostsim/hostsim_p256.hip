@@ -143,6 +143,27 @@ int hp_verify(const uint8_t* pk, const uint8_t* h, const uint8_t* gamma, const u
   PtW V = sw_straus_sc(th.data(), tg.data(), 1, s, c, sw_challenge_windows(g_str));
   return p256_verify_finish_item(U, V, enc, c, ad, ad_len, g_str);
 }
+// U and V of that verification as k_p256_verify_mul computes them and k_p256_test_verify_uv_readout writes them (Sec1; the
+// point at infinity as 33 zero bytes).  0, or 2 with zero bytes in u and v.
+int hp_verify_uv(uint32_t challenge_len, const uint8_t* pk, const uint8_t* h, const uint8_t* gamma, const uint8_t* c_be,
+                 const uint8_t* s_be, uint8_t* u, uint8_t* v) {
+  SuiteStr str = g_str;
+  str.challenge_len = challenge_len;
+  FeN x[3], y[3]; Sec1W enc[3]; uint32_t c[8], s[8];
+  memset(u, 0, 33); memset(v, 0, 33);
+  if (!p256_verify_decode_item(x, y, enc, c, s, pk, h, gamma, c_be, s_be, str.challenge_len)) return 2;
+  std::vector<uint32_t> ty(SW_TABLE_WORDS), th(SW_TABLE_WORDS), tg(SW_TABLE_WORDS);
+  sw_build_table(ty.data(), 1, sw_from_affine(x[0], y[0]));
+  sw_build_table(th.data(), 1, sw_from_affine(x[1], y[1]));
+  sw_build_table(tg.data(), 1, sw_from_affine(x[2], y[2]));
+  const PtW uv[2] = {sw_comb_minus_win(comb().data(), ty.data(), 1, s, c, sw_challenge_windows(str)),
+                     sw_straus_sc(th.data(), tg.data(), 1, s, c, sw_challenge_windows(str))};
+  Sec1W w[2];
+  sw_to_sec1<false>(w, uv);
+  if (w[0].tag) sec1_store(u, w[0].tag, w[0].xw);
+  if (w[1].tag) sec1_store(v, w[1].tag, w[1].xw);
+  return 0;
+}
 // ---- Pedersen, staged as k_p256.hip stages it ----
 void hp_set_blinding_base(const uint8_t* xy) {       // affine big-endian x || y
   g_comb_b.assign(P256_COMB_WORDS, 0);

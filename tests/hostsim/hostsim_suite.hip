@@ -49,6 +49,7 @@ HostTablesX& HX() { static HostTablesX h; h.t.sq.str = g_hx_str; return h; }
 static FeN in(const uint8_t* b) { uint32_t w[8]; memcpy(w, b, 32); return fe_from_u256(w); }
 template <int L, int V> static void out(uint8_t* b, const Fe<L, V>& a) { uint32_t w[8]; fe_to_u256(w, a); memcpy(b, w, 32); }
 }
+#include "verify_uv.inc"
 static uint32_t g_check_mask_x = 0;   // CHK_* bits for the decode stages (0 = on-curve only)
 extern "C" {
 void hx_set_check_mask(uint32_t m) { g_check_mask_x = m; }
@@ -199,6 +200,10 @@ uint32_t hx_ietf_verify(const uint8_t* pk, const uint8_t* h, const uint8_t* g, c
   verify_straus_item<SX, 0>(uv.data(), HX().t, tabs.data(), c2, s2);
   verify_straus_item<SX, 1>(uv.data() + UV_WORDS, HX().t, tabs.data(), c2, s2);
   return verify_finish_item<SX>(uv.data(), w[0], w[1], w[2], w[3], w[4], valid, ad, ad_len, g_hx_str);
+}
+uint32_t hx_verify_uv(uint32_t challenge_len, const uint8_t* pk, const uint8_t* h, const uint8_t* g, const uint8_t* c,
+                      const uint8_t* s, uint8_t* u, uint8_t* v) {
+  return host_verify_uv<SX>(HX().t, challenge_len, g_check_mask_x, pk, h, g, c, s, u, v);
 }
 uint32_t hx_pedersen_verify(const uint8_t* h, const uint8_t* g, const uint8_t* proof160, const uint8_t* ad, uint32_t ad_len) {
   uint32_t enc[5][8], s[8], sb[8], c[8];

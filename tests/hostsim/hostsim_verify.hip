@@ -32,6 +32,7 @@ struct HostTables {
 };
 HostTables& HT() { static HostTables h; h.t.sq.str = g_hs_str; return h; }      // strings may change between calls
 }
+#include "verify_uv.inc"
 static uint32_t g_check_mask = 0;      // CHK_* bits applied by the decode stages below (0 = on-curve only)
 extern "C" {
 void hs_set_check_mask(uint32_t m) { g_check_mask = m; }
@@ -45,6 +46,11 @@ uint32_t hs_ietf_verify(const uint8_t* pk, const uint8_t* h, const uint8_t* g, c
   verify_straus_item<SuiteBS, 0>(uv.data(), HT().t, tabs.data(), w[3], w[4]);
   verify_straus_item<SuiteBS, 1>(uv.data() + UV_WORDS, HT().t, tabs.data(), w[3], w[4]);
   return verify_finish_item<SuiteBS>(uv.data(), w[0], w[1], w[2], w[3], w[4], valid, ad, ad_len, g_hs_str);
+}
+// U and V of that verification (verify_uv.inc), Bandersnatch
+uint32_t hs_verify_uv(uint32_t challenge_len, const uint8_t* pk, const uint8_t* h, const uint8_t* g, const uint8_t* c,
+                      const uint8_t* s, uint8_t* u, uint8_t* v) {
+  return host_verify_uv<SuiteBS>(HT().t, challenge_len, g_check_mask, pk, h, g, c, s, u, v);
 }
 // GLV pieces: k -> (k1, k2) as 2 x (16 B magnitude, 1 B sign) ; psi(P) encoded
 void hs_glv_decompose(const uint8_t* k, uint8_t* out34) {
