@@ -37,6 +37,8 @@ SYMBOLS = [
     "vrfhip_g1_decode_batch", "vrfhip_g1_decode_batch_dev", "vrfhip_g1_validate_batch", "vrfhip_g1_validate_batch_dev",
     "vrfhip_g1_encode_batch", "vrfhip_g1_encode_batch_dev", "vrfhip_g1_lincomb_batch", "vrfhip_g1_lincomb_batch_dev",
     "vrfhip_kzg_check_batch", "vrfhip_kzg_check_batch_dev", "vrfhip_kzg_check_batch_rlc", "vrfhip_kzg_check_batch_rlc_dev",
+    "vrfhip_kzg_multi_check_batch", "vrfhip_kzg_multi_check_batch_dev", "vrfhip_kzg_multi_check_batch_rlc",
+    "vrfhip_kzg_multi_check_batch_rlc_dev",
     "vrfhip_hash_to_curve_batch", "vrfhip_hash_to_curve_batch_dev",
     "vrfhip_output_hash_batch", "vrfhip_output_hash_batch_dev",
     "vrfhip_secret_from_seed_batch", "vrfhip_secret_from_seed_batch_dev",
@@ -183,6 +185,11 @@ def load() -> ctypes.CDLL:
     lib.vrfhip_kzg_check_batch_dev.argtypes = [c_void_p, c_size_t, P, P, P, P, P, P, c_void_p]
     lib.vrfhip_kzg_check_batch_rlc.argtypes = [c_void_p, c_size_t, P, P, P, P, P, P, P, POINTER(c_int32)]
     lib.vrfhip_kzg_check_batch_rlc_dev.argtypes = [c_void_p, c_size_t, P, P, P, P, P, P, P, P, P, c_void_p]
+    kzgm = [c_void_p, c_size_t, c_uint32, c_uint32, c_uint32] + [P] * 8    # ctx, n, (k, m, p), the seven arrays, vk
+    lib.vrfhip_kzg_multi_check_batch.argtypes = kzgm + [P]
+    lib.vrfhip_kzg_multi_check_batch_dev.argtypes = kzgm + [P, c_void_p]
+    lib.vrfhip_kzg_multi_check_batch_rlc.argtypes = kzgm + [P, P, POINTER(c_int32)]
+    lib.vrfhip_kzg_multi_check_batch_rlc_dev.argtypes = kzgm + [P, P, P, P, c_void_p]
     lib.vrfhip_hash_to_curve_batch.argtypes = [c_void_p, c_size_t, P, P, c_uint32, P]
     lib.vrfhip_hash_to_curve_batch_dev.argtypes = [c_void_p, c_size_t, P, P, c_uint32, P, c_void_p]
     lib.vrfhip_output_hash_batch.argtypes = [c_void_p, c_size_t, P, P]

@@ -776,6 +776,90 @@ class Context:
                                                             None if sums is None else sums.data_ptr(), st),
                    "vrfhip_kzg_check_batch_rlc_dev")
 
+    @staticmethod
+    def _kzg_multi_shape(n, commitments, scalars, shared_bases, shared_scalars, proofs, points, coefs):
+        """(k, m, p) from the arrays' second dimensions -- arrays or tensors of shape (n, count, width), None = count 0 --
+        checked against each other"""
+        def count(a, w):
+            if a is None:
+                return 0
+            return a.shape[1] if a.ndim == 3 and a.shape[0] == n and a.shape[2] == w else -1
+        k, p = count(commitments, 48), count(proofs, 48)
+        m = 0 if shared_bases is None else shared_bases.shape[0]
+        if k < 0 or p < 1 or count(scalars, 32) != k or count(points, 32) != p or count(coefs, 32) != p or \
+                count(shared_scalars, 32) != m + 1 or (m and tuple(shared_bases.shape) != (m, 96)):
+            raise ValueError("ragged batch: commitments / scalars (n, k, 48 / 32), shared_bases (m, 96), shared_scalars "
+                             "(n, m + 1, 32), proofs / points / coefs (n, p, 48 / 32 / 32) with p >= 1")
+        if k + p + m + 1 > 16:
+            raise ValueError("k + p + m + 1 must be <= 16")
+        return k, m, p
+
+    def _kzg_multi_host_args(self, commitments, scalars, shared_bases, shared_scalars, proofs, points, coefs, vk):
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.uint8)
+                for a in (commitments, scalars, shared_bases, shared_scalars, proofs, points, coefs)]
+        for j in (0, 1):                         # (n, 0, width) counts as absent, and so does an empty shared_bases
+            if arrs[j] is not None and arrs[j].ndim == 3 and arrs[j].shape[1] == 0:
+                arrs[j] = None
+        if arrs[2] is not None and arrs[2].size == 0:
+            arrs[2] = None
+        if arrs[3] is None or arrs[3].ndim != 3:
+            raise ValueError("shared_scalars must have shape (n, m + 1, 32)")
+        n = arrs[3].shape[0]
+        return n, self._kzg_multi_shape(n, *arrs), arrs, _np_u8(vk, 480)
+
+    def kzg_multi_check_batch(self, commitments, scalars, shared_bases, shared_scalars, proofs, points, coefs, vk) -> np.ndarray:
+        """Multi-commitment, multi-point KZG openings per item: e(A_i, h) e(B_i, beta_h) = 1 with A_i = sum s_ij C_ij +
+        sum t_ij S_j + sum (u_ij z_ij) pi_ij, B_i = -sum u_ij pi_ij, S_0 = vk.g.  commitments (n, k, 48) with scalars (n, k, 32)
+        (both None for k = 0), shared_bases (m, 96) or None, shared_scalars (n, m + 1, 32), proofs (n, p, 48) with points and
+        coefs (n, p, 32); k + p + m + 1 <= 16.  -> status (n,): 0 / 1 / 2."""
+        n, (k, m, p), arrs, key = self._kzg_multi_host_args(commitments, scalars, shared_bases, shared_scalars, proofs, points,
+                                                            coefs, vk)
+        st = np.empty(n, dtype=np.uint8)
+        ptr = lambda a: _ptr(a) if a is not None and a.size else None
+        _lib.check(self._lib.vrfhip_kzg_multi_check_batch(self._h, n, k, m, p, *[ptr(a) for a in arrs], _ptr(key), ptr(st)),
+                   "vrfhip_kzg_multi_check_batch")
+        return st
+
+    def kzg_multi_check_batch_dev(self, commitments, scalars, shared_bases, shared_scalars, proofs, points, coefs, vk, status,
+                                  stream=None):
+        """Device form: tensors of the shapes above (None for an array whose count is 0), vk (480,), status (n,)."""
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        arrs = [commitments, scalars, shared_bases, shared_scalars, proofs, points, coefs]
+        k, m, p = self._kzg_multi_shape(status.shape[0], *arrs)
+        dp = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self._lib.vrfhip_kzg_multi_check_batch_dev(self._h, status.shape[0], k, m, p, *[dp(a) for a in arrs],
+                                                              vk.data_ptr(), status.data_ptr(), st),
+                   "vrfhip_kzg_multi_check_batch_dev")
+
+    def kzg_multi_check_batch_rlc(self, commitments, scalars, shared_bases, shared_scalars, proofs, points, coefs, vk,
+                                  seed: Optional[bytes] = None):
+        """The same n items as ONE equation: two G1 MSMs, m + 1 sums in Fr and one pairing; a failing batch is re-checked per
+        item.  -> (status, batch_ok)"""
+        import os as _os
+        n, (k, m, p), arrs, key = self._kzg_multi_host_args(commitments, scalars, shared_bases, shared_scalars, proofs, points,
+                                                            coefs, vk)
+        sd = _np_u8(seed if seed is not None else _os.urandom(32), 32)
+        st = np.empty(n, dtype=np.uint8)
+        okf = ctypes.c_int32(1)
+        ptr = lambda a: _ptr(a) if a is not None and a.size else None
+        _lib.check(self._lib.vrfhip_kzg_multi_check_batch_rlc(self._h, n, k, m, p, *[ptr(a) for a in arrs], _ptr(key), _ptr(sd),
+                                                              ptr(st), ctypes.byref(okf)), "vrfhip_kzg_multi_check_batch_rlc")
+        return st, bool(okf.value)
+
+    def kzg_multi_check_batch_rlc_dev(self, commitments, scalars, shared_bases, shared_scalars, proofs, points, coefs, vk, status,
+                                      verdict, seed: bytes, sums=None, stream=None):
+        """Device form: status (n,) gets 0 / 2, verdict (1,) 0 / 1 / 2; sums (192,), optional, receives S_A || S_B."""
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        arrs = [commitments, scalars, shared_bases, shared_scalars, proofs, points, coefs]
+        k, m, p = self._kzg_multi_shape(status.shape[0], *arrs)
+        sd = _np_u8(seed, 32)
+        dp = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self._lib.vrfhip_kzg_multi_check_batch_rlc_dev(self._h, status.shape[0], k, m, p, *[dp(a) for a in arrs],
+                                                                  vk.data_ptr(), _ptr(sd), status.data_ptr(), verdict.data_ptr(),
+                                                                  dp(sums), st), "vrfhip_kzg_multi_check_batch_rlc_dev")
+
     def hash_to_curve_batch(self, msgs) -> np.ndarray:
         if isinstance(msgs, np.ndarray):
             m = np.ascontiguousarray(msgs, dtype=np.uint8)

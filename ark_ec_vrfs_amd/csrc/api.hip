@@ -2281,6 +2281,251 @@ int32_t vrfhip_kzg_check_batch_rlc(vrfhip_ctx* ctx, size_t n, const uint8_t* com
   return VRFHIP_SUCCESS;
 }
 
+// ------------------------------------------------------------------------- multi-point KZG openings (k_kzg_multi.hip)
+}  // extern "C"
+
+namespace {
+// the shape and the caller's arrays of one call, in the header's order
+struct KzgmArgs {
+  uint32_t k, m, p;
+  const uint8_t *c, *s, *sb, *t, *pi, *z, *u, *vk;
+  size_t terms() const { return size_t(k) + p; }
+};
+// the argument rules all four forms share: the shape first, then n = 0, then the arrays -- one whose count is 0 may be NULL.
+// *empty: the call is done.
+int32_t kzgm_args(vrfhip_ctx* ctx, size_t n, const KzgmArgs& a, const uint8_t* status, bool* empty) {
+  *empty = n == 0;
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
+  if (a.p < 1 || a.k > 16 || a.m > 16 || a.p > 16 || a.k + a.p + a.m + 1 > 16)
+    return fail(VRFHIP_ERR_BAD_ARG, "the shape needs p >= 1 and k + p + m + 1 <= 16");
+  if (n > (size_t(1) << 28) || n * a.terms() + a.m + 1 > (size_t(1) << 28)) return fail(VRFHIP_ERR_BAD_ARG, "batch too large");
+  if (n == 0) return VRFHIP_SUCCESS;
+  if ((a.k && (!a.c || !a.s)) || (a.m && !a.sb) || !a.t || !a.pi || !a.z || !a.u || !a.vk || !status)
+    return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  return VRFHIP_SUCCESS;
+}
+// n points through the checked decode, launches of G1_CODEC_CHUNK
+void kzgm_decode(size_t n, const uint8_t* p48, uint8_t* d_xy, uint8_t* d_dec, hipStream_t st) {
+  for_chunks(n, G1_CODEC_CHUNK, [&](size_t base, size_t cnt) -> int32_t {
+    launch_g1_decode(cnt, p48 + base * 48, true, d_xy + base * 96, d_dec + base, st);
+    return VRFHIP_SUCCESS;
+  });
+}
+// the host-pointer forms' staging: the arrays, statuses, verdict
+struct KzgmStage {
+  uint8_t *c, *s, *sb, *t, *pi, *z, *u, *vk, *st, *verdict;
+  void take(Stage& sg, size_t n, const KzgmArgs& a) {
+    c = sg.take(n * a.k * 48); s = sg.take(n * a.k * 32); sb = sg.take(size_t(a.m) * 96); t = sg.take(n * (a.m + 1) * 32);
+    pi = sg.take(n * a.p * 48); z = sg.take(n * a.p * 32); u = sg.take(n * a.p * 32);
+    vk = sg.take(KZG_VK_BYTES); st = sg.take(n); verdict = sg.take(1);
+  }
+  KzgmArgs args(const KzgmArgs& a) const { return KzgmArgs{a.k, a.m, a.p, c, s, sb, t, pi, z, u, vk}; }
+};
+int32_t kzgm_send(vrfhip_ctx* ctx, const KzgmStage& d, size_t n, const KzgmArgs& a) {
+  if (a.k) {
+    HIP_TRY(hipMemcpyAsync(d.c, a.c, n * a.k * 48, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d.s, a.s, n * a.k * 32, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (a.m) HIP_TRY(hipMemcpyAsync(d.sb, a.sb, size_t(a.m) * 96, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(d.t, a.t, n * (a.m + 1) * 32, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(d.pi, a.pi, n * a.p * 48, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(d.z, a.z, n * a.p * 32, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(d.u, a.u, n * a.p * 32, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(d.vk, a.vk, KZG_VK_BYTES, hipMemcpyHostToDevice, ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+// vk || shared_bases contiguously at d_key: the digest leaves' common byte string; the fold kernel reads g at d_key and
+// S_1 .. S_m at d_key + 480
+int32_t kzgm_stage_key(const KzgmArgs& a, uint8_t* d_key, hipStream_t st) {
+  HIP_TRY(hipMemcpyAsync(d_key, a.vk, KZG_VK_BYTES, hipMemcpyDeviceToDevice, st));
+  if (a.m) HIP_TRY(hipMemcpyAsync(d_key + KZG_VK_BYTES, a.sb, size_t(a.m) * 96, hipMemcpyDeviceToDevice, st));
+  return VRFHIP_SUCCESS;
+}
+
+int32_t kzgm_check_dev(vrfhip_ctx* ctx, size_t n, const KzgmArgs& a, uint8_t* d_status, hipStream_t st) {
+  // decode -> rows -> two linear combinations -> pairing, a launch group of at most KZG_ITEM_CHUNK items at a time through
+  // the workspace: decoded C | decoded pi | decode statuses (C, pi) | rows of A_i (bases, scalars, shared scalars) | rows of
+  // B_i (bases, scalars) | pairing items | g, S_1 .. S_m contiguously
+  const size_t cap = std::min(n, KZG_ITEM_CHUNK), T = a.terms();
+  Stage carve(nullptr);
+  auto layout = [&](Stage& sg, uint8_t** w) {
+    w[0] = sg.take(cap * a.k * 96); w[1] = sg.take(cap * a.p * 96); w[2] = sg.take(cap * a.k); w[3] = sg.take(cap * a.p);
+    w[4] = sg.take(cap * T * 96); w[5] = sg.take(cap * T * 32); w[6] = sg.take(cap * (a.m + 1) * 32);
+    w[7] = sg.take(cap * a.p * 96); w[8] = sg.take(cap * a.p * 32); w[9] = sg.take(cap * 192);
+    w[10] = sg.take(size_t(a.m + 1) * 96);
+  };
+  uint8_t* w[11];
+  layout(carve, w);
+  int32_t rc = ensure_msm_workspace(ctx, carve.off);
+  if (rc) return rc;
+  Stage sg(ctx->d_msm_ws);
+  layout(sg, w);
+  HIP_TRY(hipMemcpyAsync(w[10], a.vk, 96, hipMemcpyDeviceToDevice, st));
+  if (a.m) HIP_TRY(hipMemcpyAsync(w[10] + 96, a.sb, size_t(a.m) * 96, hipMemcpyDeviceToDevice, st));
+  for_chunks(n, cap, [&](size_t base, size_t cnt) -> int32_t {
+    kzgm_decode(cnt * a.k, at(a.c, base, size_t(a.k) * 48), w[0], w[2], st);
+    kzgm_decode(cnt * a.p, a.pi + base * a.p * 48, w[1], w[3], st);
+    KzgMultiArrays in{w[0], at(a.s, base, size_t(a.k) * 32), a.t + base * (a.m + 1) * 32, w[1], a.z + base * a.p * 32,
+                      a.u + base * a.p * 32, w[2], w[3]};
+    launch_kzg_multi_item_rows(cnt, a.k, a.m, a.p, in, w[4], w[5], w[6], w[7], w[8], st);
+    launch_g1_lincomb(cnt, (uint32_t)T, w[4], w[5], a.m + 1, w[10], w[6], w[9], 192, d_status + base, st);       // A_i
+    launch_g1_lincomb(cnt, a.p, w[7], w[8], 0, nullptr, nullptr, w[9] + 96, 192, d_status + base, st);         // B_i
+    launch_pairing_check2(cnt, w[9], a.vk + 96, 0, d_status + base, st, ctx->d_pair_prep, ctx->dbg_pairing_layout);
+    return VRFHIP_SUCCESS;
+  });
+  HIP_TRY(hipGetLastError());
+  return VRFHIP_SUCCESS;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t vrfhip_kzg_multi_check_batch_dev(vrfhip_ctx* ctx, size_t n, uint32_t k, uint32_t m, uint32_t p,
+                                         const uint8_t* d_commitments48, const uint8_t* d_scalars32,
+                                         const uint8_t* d_shared_bases, const uint8_t* d_shared_scalars32,
+                                         const uint8_t* d_proofs48, const uint8_t* d_points32, const uint8_t* d_coefs32,
+                                         const uint8_t* d_vk, uint8_t* d_status, void* stream) {
+  const KzgmArgs a{k, m, p, d_commitments48, d_scalars32, d_shared_bases, d_shared_scalars32, d_proofs48, d_points32, d_coefs32,
+                   d_vk};
+  bool empty;
+  int32_t rc = kzgm_args(ctx, n, a, d_status, &empty);
+  if (rc || empty) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  return kzgm_check_dev(ctx, n, a, d_status, static_cast<hipStream_t>(stream));
+}
+
+int32_t vrfhip_kzg_multi_check_batch(vrfhip_ctx* ctx, size_t n, uint32_t k, uint32_t m, uint32_t p, const uint8_t* commitments48,
+                                     const uint8_t* scalars32, const uint8_t* shared_bases, const uint8_t* shared_scalars32,
+                                     const uint8_t* proofs48, const uint8_t* points32, const uint8_t* coefs32, const uint8_t* vk,
+                                     uint8_t* status) {
+  const KzgmArgs a{k, m, p, commitments48, scalars32, shared_bases, shared_scalars32, proofs48, points32, coefs32, vk};
+  bool empty;
+  int32_t rc = kzgm_args(ctx, n, a, status, &empty);
+  if (rc || empty) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  KzgmStage d;
+  rc = stage_layout(ctx, [&](Stage& sg) { d.take(sg, n, a); });
+  if (rc) return rc;
+  if ((rc = kzgm_send(ctx, d, n, a))) return rc;
+  rc = kzgm_check_dev(ctx, n, d.args(a), d.st, ctx->stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(status, d.st, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+
+int32_t vrfhip_kzg_multi_check_batch_rlc_dev(vrfhip_ctx* ctx, size_t n, uint32_t k, uint32_t m, uint32_t p,
+                                             const uint8_t* d_commitments48, const uint8_t* d_scalars32,
+                                             const uint8_t* d_shared_bases, const uint8_t* d_shared_scalars32,
+                                             const uint8_t* d_proofs48, const uint8_t* d_points32, const uint8_t* d_coefs32,
+                                             const uint8_t* d_vk, const uint8_t seed[32], uint8_t* d_status, uint8_t* d_verdict,
+                                             uint8_t* d_sums, void* stream) {
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
+  if (!d_verdict || !seed) return fail(VRFHIP_ERR_BAD_ARG, "NULL verdict or seed");
+  const KzgmArgs a{k, m, p, d_commitments48, d_scalars32, d_shared_bases, d_shared_scalars32, d_proofs48, d_points32, d_coefs32,
+                   d_vk};
+  bool empty;
+  int32_t rc = kzgm_args(ctx, n, a, d_status, &empty);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (empty) {                                    // the empty batch holds; its sums are the point at infinity twice
+    HIP_TRY(hipMemsetAsync(d_verdict, 0, 1, st));
+    if (d_sums) HIP_TRY(hipMemsetAsync(d_sums, 0, 192, st));
+    return VRFHIP_SUCCESS;
+  }
+  // workspace: layout A (own terms, then g, S_*) | layout B (proofs) | digest tree | root | vk || shared_bases | weights |
+  // partial sums | the pairing item | decoded C | decoded pi | decode statuses (C, pi)
+  const size_t T = a.terms(), na = n * T + m + 1, nb = n * p;
+  const int ga = g1_msm_groups(na, 1, G1_W_FULL, ctx->cus), gb = g1_msm_groups(nb, 1, G1_W_FULL, ctx->cus);
+  uint8_t *w_a, *w_b, *d_digest_ws, *d_root, *d_key, *d_wts, *d_part, *d_item, *d_c, *d_p, *d_dec_c, *d_dec_p;
+  auto layout = [&](Stage& sg) {
+    w_a = sg.take(g1_msm_workspace_bytes(na, 1, G1_W_FULL, ga));
+    w_b = sg.take(g1_msm_workspace_bytes(nb, 1, G1_W_FULL, gb));
+    d_digest_ws = sg.take(digest_ws_bytes(n));
+    d_root = sg.take(32);
+    d_key = sg.take(KZG_VK_BYTES + size_t(m) * 96);
+    d_wts = sg.take(n * 4 * sizeof(uint32_t));
+    d_part = sg.take(size_t(m + 1) * kzg_partials(n) * KZG_PART_WORDS * sizeof(uint32_t));
+    d_item = sg.take(192);
+    d_c = sg.take(n * k * 96); d_p = sg.take(n * p * 96); d_dec_c = sg.take(n * k); d_dec_p = sg.take(n * p);
+  };
+  Stage measure(nullptr);
+  layout(measure);
+  rc = ensure_msm_workspace(ctx, measure.off);    // a call that does not fit ends here: VRFHIP_ERR_OOM, no array touched
+  if (rc) return rc;
+  Stage sg(ctx->d_msm_ws);
+  layout(sg);
+  HIP_TRY(hipMemsetAsync(d_verdict, 0, 1, st));
+  const G1MsmLayout A = g1_msm_layout(na, 1, G1_W_FULL, ga, w_a), B = g1_msm_layout(nb, 1, G1_W_FULL, gb, w_b);
+  hipEvent_t* ev = prof_events(ctx);            // start | decode | prep (digest, prep, fold) | buckets | final, combine
+  if (ev) (void)hipEventRecord(ev[0], st);
+  kzgm_decode(n * k, d_commitments48, d_c, d_dec_c, st);
+  kzgm_decode(n * p, d_proofs48, d_p, d_dec_p, st);
+  if ((rc = kzgm_stage_key(a, d_key, st))) return rc;
+  if (ev) (void)hipEventRecord(ev[1], st);
+  // the weights depend on every byte the caller handed over, as it arrived, on the key and on the shared bases
+  DigestSrc ds{};
+  const uint8_t* arr[6] = {d_commitments48, d_scalars32, d_shared_scalars32, d_proofs48, d_points32, d_coefs32};
+  const uint32_t width[6] = {48 * k, 32 * k, 32 * (m + 1), 48 * p, 32 * p, 32 * p};
+  int na_arr = 0;
+  for (int j = 0; j < 6; ++j)
+    if (width[j]) { ds.p[na_arr] = arr[j]; ds.w[na_arr] = width[j]; ++na_arr; }      // k = 0: the two k-arrays are left out
+  ds.n_arr = na_arr;
+  ds.ad = Blob{d_key, nullptr, (uint32_t)(KZG_VK_BYTES + size_t(m) * 96), true}.view(0);
+  launch_batch_digest(ds, n, 0, d_digest_ws, d_root, st);
+  const KzgMultiArrays in{d_c, d_scalars32, d_shared_scalars32, d_p, d_points32, d_coefs32, d_dec_c, d_dec_p};
+  launch_kzg_multi_rlc(A, B, n, k, m, p, in, d_key, d_key + KZG_VK_BYTES, seed, d_root, reinterpret_cast<uint32_t*>(d_wts),
+                       reinterpret_cast<uint32_t*>(d_part), d_status, d_item, st, ev ? ev + 2 : nullptr);
+  if (d_sums) HIP_TRY(hipMemcpyAsync(d_sums, d_item, 192, hipMemcpyDeviceToDevice, st));
+  // one pairing check for the whole batch, against the prepared lines of (h, beta_h); an invalid g or shared base left an
+  // all-0xFF item
+  launch_pairing_check2(1, d_item, d_vk + 96, 0, d_verdict, st, ctx->d_pair_prep, ctx->dbg_pairing_layout);
+  HIP_TRY(hipGetLastError());
+  return VRFHIP_SUCCESS;
+}
+
+int32_t vrfhip_kzg_multi_check_batch_rlc(vrfhip_ctx* ctx, size_t n, uint32_t k, uint32_t m, uint32_t p,
+                                         const uint8_t* commitments48, const uint8_t* scalars32, const uint8_t* shared_bases,
+                                         const uint8_t* shared_scalars32, const uint8_t* proofs48, const uint8_t* points32,
+                                         const uint8_t* coefs32, const uint8_t* vk, const uint8_t seed[32], uint8_t* status,
+                                         int32_t* batch_ok) {
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
+  if (!seed) return fail(VRFHIP_ERR_BAD_ARG, "seed is NULL");
+  if (batch_ok) *batch_ok = 1;
+  const KzgmArgs a{k, m, p, commitments48, scalars32, shared_bases, shared_scalars32, proofs48, points32, coefs32, vk};
+  bool empty;
+  int32_t rc = kzgm_args(ctx, n, a, status, &empty);
+  if (rc || empty) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  KzgmStage d;
+  rc = stage_layout(ctx, [&](Stage& sg) { d.take(sg, n, a); });
+  if (rc) return rc;
+  if ((rc = kzgm_send(ctx, d, n, a))) return rc;
+  rc = vrfhip_kzg_multi_check_batch_rlc_dev(ctx, n, k, m, p, d.c, d.s, d.sb, d.t, d.pi, d.z, d.u, d.vk, seed, d.st, d.verdict,
+                                            nullptr, ctx->stream);
+  if (rc) return rc;
+  uint8_t verdict = 0;
+  HIP_TRY(hipMemcpyAsync(&verdict, d.verdict, 1, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (verdict != 0) {
+    // some item is false (or the key or a shared base is invalid): the per-item form names it
+    if (batch_ok) *batch_ok = 0;
+    rc = kzgm_check_dev(ctx, n, d.args(a), d.st, ctx->stream);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(status, d.st, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+
 // Test-only: quad-distributed Fp12 tower operations against the one-lane operations (k_pairing.hip)
 int32_t vrfhip_test_pairing_quad_ops(vrfhip_ctx* ctx, size_t n, const uint8_t* fp12_pairs, uint8_t* status) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");

@@ -91,4 +91,32 @@ void launch_kzg_rlc(const G1MsmLayout& S, const G1MsmLayout& F, const uint8_t* g
                     const uint8_t* v, const uint8_t* vk, const uint8_t seed[32], const uint8_t* d_root, uint32_t* partials,
                     uint8_t* status, uint8_t* item192, hipStream_t st, hipEvent_t* ev = nullptr);
 
+// Multi-commitment, multi-point KZG openings (k_kzg_multi.hip, kzg_multi.cuh), shape (k, m, p) per call: k own commitments,
+// the shared bases g, S_1 .. S_m and p proofs per item, k + p + m + 1 <= 16, p >= 1.  The arrays of n items, 4-byte aligned:
+struct KzgMultiArrays {
+  const uint8_t* g1c;             // n k x 96 B decoded commitments (launch_g1_decode; an invalid one is all-0xFF)
+  const uint8_t* scalars;         // n k x 32 B        s_ij
+  const uint8_t* shared_scalars;  // n (m + 1) x 32 B  t_i0 (for g), t_i1 .. t_im
+  const uint8_t* g1p;             // n p x 96 B decoded proofs
+  const uint8_t* points;          // n p x 32 B        z_ij
+  const uint8_t* coefs;           // n p x 32 B        u_ij
+  const uint8_t *dec_c, *dec_p;   // the n k and n p decode statuses
+};
+// Per-item form: the rows of two launch_g1_lincomb calls.  A_i: bases_a n (k + p) x 96 B = [C_i*, pi_i*] under scalars_a
+// = [s_ij, u_ij z_ij mod r], shared terms [g, S_*] under shared_a = t_i*; B_i: bases_b n p x 96 B = pi_i* under scalars_b
+// = r - u_ij.  An item with an invalid point or a scalar >= r gets all-0xFF rows in all five arrays.
+void launch_kzg_multi_item_rows(size_t n, uint32_t k, uint32_t m, uint32_t p, const KzgMultiArrays& a, uint8_t* bases_a,
+                                uint8_t* scalars_a, uint8_t* shared_a, uint8_t* bases_b, uint8_t* scalars_b, hipStream_t st);
+// Batched form: r_i = SHA-512("vrfhip-kzg-multi-rlc-v1" || u32_le(k) || u32_le(m) || u32_le(p) || seed || d_root[32] ||
+// u64_le(i))[0..16]; fills A (sets = 1, windows = G1_W_FULL, n (k + p) + m + 1 points: the own terms item by item under
+// r_i s_ij and r_i u_ij z_ij, then g, S_1 .. S_m under sum_i r_i t_ij) and B (sets = 1, windows = G1_W_FULL, n p points: pi_ij
+// under r_i u_ij), runs both multi-scalar multiplications and writes the one pairing item A.sums || -B.sums to item192
+// (all-0xFF if g or a shared base is invalid).  status[i] = 0 / 2.  g: 96 B; shared_bases: m x 96 B (not read for m = 0).
+// weights: n * 4 words; partials: (m + 1) * kzg_partials(n) * KZG_PART_WORDS words.  ev (nullable, 3 events): after prep + fold,
+// after the buckets of both layouts, after final + combine.
+void launch_kzg_multi_rlc(const G1MsmLayout& A, const G1MsmLayout& B, size_t n, uint32_t k, uint32_t m, uint32_t p,
+                          const KzgMultiArrays& a, const uint8_t* g, const uint8_t* shared_bases, const uint8_t seed[32],
+                          const uint8_t* d_root, uint32_t* weights, uint32_t* partials, uint8_t* status, uint8_t* item192,
+                          hipStream_t st, hipEvent_t* ev = nullptr);
+
 }  // namespace vrf

@@ -584,9 +584,9 @@ int32_t vrfhip_g1_lincomb_batch_dev(vrfhip_ctx* ctx, size_t n, uint32_t k, const
  * there is no unchecked variant.  points32 (the z_i), values32 (the v_i): n x 32 B little-endian, < r.
  * vk: 480 B = g (96 B, x || y little-endian as for vrfhip_g1_msm) || h (192 B) || beta_h (192 B, both in the G2 layout of
  * vrfhip_pairing_check_batch) -- arkworks' `VerifierKey {g, h, beta_h}` as it is: the caller negates nothing, the library
- * negates on the G1 side; g is a parameter because an SRS fixes its own.  `gamma_g` and hiding openings (`random_v`), and
- * multi-point / multi-polynomial openings, are out of scope.  The Miller-loop lines of (h, beta_h) stay in the context as
- * for the shared-pair calls above, so later calls with the same key reuse them.
+ * negates on the G1 side; g is a parameter because an SRS fixes its own.  `gamma_g` and hiding openings (`random_v`) are out
+ * of scope; multi-point / multi-polynomial openings are vrfhip_kzg_multi_check_batch* below.  The Miller-loop lines of
+ * (h, beta_h) stay in the context as for the shared-pair calls above, so later calls with the same key reuse them.
  * status[i]: 0 = the opening holds, 1 = VerificationFailure, 2 = InvalidData (a bad point encoding, a point outside the
  * subgroup, z_i >= r or v_i >= r; an invalid vk makes every item InvalidData).  Infinity is a valid commitment and a valid
  * proof: the zero polynomial opens as C = infinity, v = 0, pi = infinity, a constant one as C = v g, pi = infinity.
@@ -622,6 +622,61 @@ int32_t vrfhip_kzg_check_batch_rlc_dev(vrfhip_ctx* ctx, size_t n, const uint8_t*
                                        const uint8_t* d_values32, const uint8_t* d_proofs48, const uint8_t* d_vk,
                                        const uint8_t seed[32], uint8_t* d_status, uint8_t* d_verdict, uint8_t* d_sums,
                                        void* stream);
+
+/* Multi-commitment, multi-point KZG openings -- the shape a ring proof ends in (as far as upstream is recalled, INTEGRATION.md
+ * section 4): the verifier folds its proof's column commitments and fixed columns of its key into aggregate commitments, opens
+ * them at several points and checks all openings together.  The shape (k, m, p) is fixed per call: item i has k own
+ * commitments C_ij under scalars s_ij, the shared bases S_0 = vk.g, S_1 .. S_m under t_i0 .. t_im, and p opening proofs pi_ij
+ * at points z_ij with coefficients u_ij.  k >= 0, m >= 0, p >= 1, k + p + m + 1 <= 16.  Item i holds iff
+ *     e(A_i, h) e(B_i, beta_h) = 1,
+ *     A_i = sum_j s_ij C_ij + sum_{j=0..m} t_ij S_j + sum_j (u_ij z_ij mod r) pi_ij,     B_i = -sum_j u_ij pi_ij.
+ * The plain opening above is k = 1, s = 1, m = 0, t_i0 = r - v, p = 1, u = 1; the claimed values of a multi-point opening are
+ * folded into t_i0 by the caller.
+ * commitments48: n x k x 48 B and proofs48: n x p x 48 B, compressed, ALWAYS decoded checked (curve and subgroup);
+ * scalars32: n x k x 32 B; shared_bases: m x 96 B, x || y little-endian as vrfhip_g1_msm reads them -- checked to be on the
+ * curve, their subgroup membership is the caller's precondition as for vk.g; shared_scalars32: n x (m + 1) x 32 B;
+ * points32, coefs32: n x p x 32 B; every scalar little-endian and < r; vk: 480 B as above.  The two k-arrays may be NULL for
+ * k = 0, shared_bases for m = 0.
+ * status[i]: 0 = holds, 1 = VerificationFailure, 2 = InvalidData (a bad encoding, a point outside the subgroup or a scalar
+ * >= r among the item's arrays; an invalid vk or shared base makes every item InvalidData).  Infinity is a valid commitment
+ * and a valid proof, zero a valid scalar.
+ *
+ * vrfhip_kzg_multi_check_batch*: per item -- two checked decodes, the rows, A_i and B_i by vrfhip_g1_lincomb_batch's kernel
+ * (a 255-step ladder per term), one pairing check per item.  The reference semantics and the fallback of:
+ * vrfhip_kzg_multi_check_batch_rlc*: the batch as ONE equation.  With secret 128-bit weights
+ *     r_i = SHA-512("vrfhip-kzg-multi-rlc-v1" || u32_le(k) || u32_le(m) || u32_le(p) || seed || D || u64_le(i))[0..16]  (little-endian)
+ * where D is the batch digest (vrfhip_test_batch_digest) over the arrays as they arrive -- commitments48, scalars32,
+ * shared_scalars32, proofs48, points32, coefs32, widths 48 k, 32 k, 32 (m + 1), 48 p, 32 p, 32 p, the two k-arrays left out
+ * for k = 0 -- with vk || shared_bases (480 + 96 m bytes) as the leaves' common byte string, the weights go inside the sums:
+ *     S_A = sum_ij (r_i s_ij) C_ij + sum_ij (r_i u_ij z_ij) pi_ij + sum_{j=0..m} (sum_i r_i t_ij) S_j,
+ *     S_B = -sum_ij (r_i u_ij) pi_ij,            accept  <=>  e(S_A, h) e(S_B, beta_h) = 1:
+ * two G1 multi-scalar multiplications (n (k + p) + m + 1 and n p points), m + 1 sums in Fr and one pairing, no per-item
+ * ladder.  `seed`, d_status, d_verdict, d_sums, *batch_ok and n = 0: as for vrfhip_kzg_check_batch_rlc*; verdict 2 and an
+ * all-0xFF d_sums also for an invalid shared base.
+ * n <= 2^28 and n (k + p) + m + 1 <= 2^28; the _rlc_dev form is one launch group (one digest): a batch whose workspace does
+ * not fit returns VRFHIP_ERR_OOM before any array is touched.  Device arrays 4-byte aligned.
+ * VRFHIP_ERR_UNSUPPORTED on a secp256r1 context; VRFHIP_ERR_BAD_ARG for a shape outside the bounds, a NULL array whose count
+ * is not zero, a NULL seed or verdict. */
+int32_t vrfhip_kzg_multi_check_batch(vrfhip_ctx* ctx, size_t n, uint32_t k, uint32_t m, uint32_t p, const uint8_t* commitments48,
+                                     const uint8_t* scalars32, const uint8_t* shared_bases, const uint8_t* shared_scalars32,
+                                     const uint8_t* proofs48, const uint8_t* points32, const uint8_t* coefs32, const uint8_t* vk,
+                                     uint8_t* status);
+int32_t vrfhip_kzg_multi_check_batch_dev(vrfhip_ctx* ctx, size_t n, uint32_t k, uint32_t m, uint32_t p,
+                                         const uint8_t* d_commitments48, const uint8_t* d_scalars32,
+                                         const uint8_t* d_shared_bases, const uint8_t* d_shared_scalars32,
+                                         const uint8_t* d_proofs48, const uint8_t* d_points32, const uint8_t* d_coefs32,
+                                         const uint8_t* d_vk, uint8_t* d_status, void* stream);
+int32_t vrfhip_kzg_multi_check_batch_rlc(vrfhip_ctx* ctx, size_t n, uint32_t k, uint32_t m, uint32_t p,
+                                         const uint8_t* commitments48, const uint8_t* scalars32, const uint8_t* shared_bases,
+                                         const uint8_t* shared_scalars32, const uint8_t* proofs48, const uint8_t* points32,
+                                         const uint8_t* coefs32, const uint8_t* vk, const uint8_t seed[32], uint8_t* status,
+                                         int32_t* batch_ok);
+int32_t vrfhip_kzg_multi_check_batch_rlc_dev(vrfhip_ctx* ctx, size_t n, uint32_t k, uint32_t m, uint32_t p,
+                                             const uint8_t* d_commitments48, const uint8_t* d_scalars32,
+                                             const uint8_t* d_shared_bases, const uint8_t* d_shared_scalars32,
+                                             const uint8_t* d_proofs48, const uint8_t* d_points32, const uint8_t* d_coefs32,
+                                             const uint8_t* d_vk, const uint8_t seed[32], uint8_t* d_status, uint8_t* d_verdict,
+                                             uint8_t* d_sums, void* stream);
 
 /* Building blocks --------------------------------------------------------------------- */
 

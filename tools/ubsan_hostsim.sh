@@ -38,3 +38,4 @@ cd "$ROOT"
 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 python -m pytest tests/test_hostsim.py tests/test_bls_pairing.py tests/test_jubjub.py tests/test_new_suites.py tests/test_secp256r1.py tests/test_bandersnatch_sw.py -x -q -m "not gpu"
 # the KZG host simulation (tests/hostsim_kzg) is a stand-alone program: built and run on its own, never loaded into Python
 make -C "$ROOT/tests/hostsim_kzg" ubsan
+make -C "$ROOT/tests/hostsim_kzg_multi" ubsan
