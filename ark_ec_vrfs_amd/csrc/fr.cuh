@@ -242,4 +242,38 @@ VRF_HD int scalar_digit4_128(const uint32_t rec[4], int w) {   // w in 0..31
   return (int)((word >> ((w & 7) * 4)) & 15u) - 8;
 }
 
+// The joint-table ladders of IETF verification (vrf_core.cuh) read the GLV halves bit by bit and two bits at a time.  Both
+// rely on a half being below 2^127: scalar_recode_signed4_128 above already needs it below 0x77..77 (tests/verify_uv_cases.py
+// holds the decomposition to that cap), which is what the assertion states.
+constexpr uint32_t GLV_HALF_TOP_WORD_CAP = 0x77777777u;
+static_assert(GLV_HALF_TOP_WORD_CAP < 0x80000000u, "bit 127 of a GLV half must be clear: the joint ladders start at bit 126");
+
+// bit `bit` (0..127) of a 128-bit magnitude
+VRF_HD int scalar_bit_128(const uint32_t k[4], int bit) {
+  uint32_t word = k[0];
+#pragma unroll
+  for (int i = 1; i < 4; ++i)
+    if ((bit >> 5) == i) word = k[i];
+  return (int)((word >> (bit & 31)) & 1u);
+}
+// Signed radix-4 recoding of a 128-bit magnitude below 2^127: k + 0x55..5 has the 2-bit fields (d_w + 1) with d_w in
+// [-1, 2] and sum d_w 4^w = k (a field 3 becomes -1 and carries into the next one).  k < 2^127 keeps the sum below 2^128:
+// the top digit cannot carry out.
+VRF_HD void scalar_recode_signed2_128(uint32_t out[4], const uint32_t k[4]) {
+  uint32_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    uint64_t x = (uint64_t)k[i] + 0x55555555u + c;
+    out[i] = (uint32_t)x;
+    c = (uint32_t)(x >> 32);
+  }
+}
+VRF_HD int scalar_digit2_128(const uint32_t rec[4], int w) {   // w in 0..63: value in [-1, 2]
+  uint32_t word = rec[0];
+#pragma unroll
+  for (int i = 1; i < 4; ++i)
+    if ((w >> 4) == i) word = rec[i];
+  return (int)((word >> ((w & 15) * 2)) & 3u) - 1;
+}
+
 VRF_NS_END

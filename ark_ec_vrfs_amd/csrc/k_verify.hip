@@ -5,30 +5,24 @@
 
 VRF_NS_BEGIN
 
-// the proof's scalars for the Straus stages: c mod r (upstream decodes `Proof::c` with from_le_bytes_mod_order), s as is;
-// a non-canonical s is reported InvalidData by the finish stage: keep the digits in range here
-template <class S>
-VRF_HD void load_cs_reduced(uint32_t c[8], uint32_t s[8]) {
-  uint32_t cr[8];
-  fr_reduce256<S>(cr, c);
-  const bool s_ok = fr_is_canonical<S>(s);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { c[j] = s_ok ? cr[j] : 0u; s[j] = s_ok ? s[j] : 0u; }
-}
+// load_cs_reduced (the proof's scalars as the ladders take them): vrf_core.cuh
 
-// stage 1: one lane per proof.  Decompress pk, H, Gamma; build their GLV window-table pairs.
-// VERIFY_K proofs per lane share one inversion (3K decompression denominators).
+// stage 1: one lane per proof.  Decompress pk, H, Gamma; build their window tables -- the GLV suite: the joint tables of
+// -c*Y and of V = s*H - c*Gamma (vrf_core.cuh JT_Y, JT_V; the latter takes the proof's c and s), the other suites: one
+// radix-16 table per point.  VERIFY_K proofs per lane share one inversion (3K decompression denominators).
 template <class S, int MINW>
 __global__ void __launch_bounds__(BLOCK, MINW) k_verify_decode(VerifyArgs a) {
   size_t first = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * a.k_lane;
   if (first >= a.n) return;
-  verify_decode_multi<S>(a.k_lane, a.T, first, a.n, a.pk, a.h, a.gamma, a.ws.tabs, a.ws.pts, a.ws.flags, a.check_mask);
+  verify_decode_multi<S, 3, false, S::HAS_GLV>(a.k_lane, a.T, first, a.n, a.pk, a.h, a.gamma, a.ws.tabs, a.ws.pts, a.ws.flags,
+                                               a.check_mask, a.c, a.s);
 }
 
 // Verification from alpha (`Input::new(alpha)` inside the call, as a deployed verifier holds pk, alpha and the proof):
 // H leaves hash-to-curve as affine x, y -- its encoding goes where the finish stage reads it (`enc`, 32 B per item), its
-// GLV table pair straight into slot 1 of the item's tables.  No compression, second square root or subgroup test for H:
-// it is a cofactor multiple by construction.
+// window table straight into slot 1 of the item's tables; the GLV suite parks x, y in the item's region instead, where the
+// decode stage that follows finds them for the joint table of V.  No compression, second square root or subgroup test
+// for H: it is a cofactor multiple by construction.
 template <class S>
 __global__ void __launch_bounds__(BLOCK, 2) k_verify_input_from_alpha(size_t n, BytesView msg, uint8_t* enc, uint32_t* tabs,
                                                                       DevTables T, const uint8_t* tai_ctr) {
@@ -42,15 +36,16 @@ __global__ void __launch_bounds__(BLOCK, 2) k_verify_input_from_alpha(size_t n, 
   uint32_t e[8];
   te_encode_affine(e, x, y, T.sq.str.flags);
   store32(enc, i, e);
-  build_glv_tables<S>(tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS) + 2 * WIN_TABLE_WORDS, x, y);
+  if constexpr (S::HAS_GLV) jt_park_xy(tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS) + JT_HXY, x, y);
+  else build_glv_tables<S>(tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS) + 2 * WIN_TABLE_WORDS, x, y);
 }
 // stage 1 after it: pk and Gamma only
 template <class S, int MINW>
 __global__ void __launch_bounds__(BLOCK, MINW) k_verify_decode_skip_h(VerifyArgs a) {
   size_t first = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * a.k_lane;
   if (first >= a.n) return;
-  verify_decode_multi<S, 2, true>(a.k_lane, a.T, first, a.n, a.pk, nullptr, a.gamma, a.ws.tabs, a.ws.pts, a.ws.flags,
-                                  a.check_mask);
+  verify_decode_multi<S, 2, true, S::HAS_GLV>(a.k_lane, a.T, first, a.n, a.pk, nullptr, a.gamma, a.ws.tabs, a.ws.pts,
+                                              a.ws.flags, a.check_mask, a.c, a.s);
 }
 
 // stage 1, keyed: only H and Gamma are decompressed; validity also requires a valid, existing key
@@ -58,8 +53,8 @@ template <class S, int MINW>
 __global__ void __launch_bounds__(BLOCK, MINW) k_verify_decode_keyed(VerifyArgs a) {
   size_t first = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * a.k_lane;
   if (first >= a.n) return;
-  verify_decode_multi<S, 2>(a.k_lane, a.T, first, a.n, nullptr, a.h, a.gamma, a.ws.tabs, a.ws.pts, a.ws.flags,
-                            a.check_mask);
+  verify_decode_multi<S, 2, false, S::HAS_GLV>(a.k_lane, a.T, first, a.n, nullptr, a.h, a.gamma, a.ws.tabs, a.ws.pts,
+                                               a.ws.flags, a.check_mask, a.c, a.s);
 #pragma unroll 1
   for (int k = 0; k < a.k_lane; ++k) {
     const size_t i = first + k;
@@ -97,8 +92,13 @@ __global__ void __launch_bounds__(BLOCK) k_verify_decode_affine(VerifyArgs a) {
   const uint32_t* p2 = reinterpret_cast<const uint32_t*>(a.gamma + i * 64);
 #pragma unroll
   for (int j = 0; j < 16; ++j) { xy[0][j] = p0[j]; xy[1][j] = p1[j]; xy[2][j] = p2[j]; }
-  bool ok = verify_decode_affine_item<S>(enc, xy, a.ws.tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS), a.T.sq, a.check_mask,
-                                         a.affine_in == 2);
+  uint32_t c[8], s[8];
+  if constexpr (S::HAS_GLV) {
+    load32(c, a.c, i); load32(s, a.s, i);
+    load_cs_reduced<S>(c, s);
+  }
+  bool ok = verify_decode_affine_item<S, S::HAS_GLV>(enc, xy, a.ws.tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS), a.T.sq,
+                                                     a.check_mask, a.affine_in == 2, c, s);
   uint32_t* aux = a.ws.aux + i * AUX_WORDS;
 #pragma unroll
   for (int j = 0; j < 8; ++j) { aux[j] = enc[0][j]; aux[8 + j] = enc[1][j]; aux[16 + j] = enc[2][j]; }
@@ -113,8 +113,10 @@ __global__ void __launch_bounds__(BLOCK) k_verify_straus(VerifyArgs a) {
   uint32_t c[8], s[8];
   load32(c, a.c, i); load32(s, a.s, i);
   load_cs_reduced<S>(c, s);
-  verify_straus_item<S, HALF>(a.ws.pts + i * PROVE_PTS_WORDS + HALF * UV_WORDS, a.T,
-                                    a.ws.tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS), c, s);
+  uint32_t* out = a.ws.pts + i * PROVE_PTS_WORDS + HALF * UV_WORDS;
+  const uint32_t* tabs = a.ws.tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS);
+  if constexpr (S::HAS_GLV) verify_joint_item<S, HALF>(out, a.T, tabs, c, s);
+  else verify_straus_item<S, HALF>(out, a.T, tabs, c, s);
 }
 
 // stage 2 for small batches: both halves in one launch (blockIdx.y = 0: V, 1: U).  Below two waves per SIMD a
@@ -127,8 +129,13 @@ __global__ void __launch_bounds__(BLOCK) k_verify_straus_both(VerifyArgs a) {
   load32(c, a.c, i); load32(s, a.s, i);
   load_cs_reduced<S>(c, s);
   const uint32_t* tabs = a.ws.tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS);
-  if (blockIdx.y == 0) verify_straus_item<S, 1>(a.ws.pts + i * PROVE_PTS_WORDS + UV_WORDS, a.T, tabs, c, s);
-  else verify_straus_item<S, 0>(a.ws.pts + i * PROVE_PTS_WORDS, a.T, tabs, c, s);
+  if constexpr (S::HAS_GLV) {
+    if (blockIdx.y == 0) verify_joint_item<S, 1>(a.ws.pts + i * PROVE_PTS_WORDS + UV_WORDS, a.T, tabs, c, s);
+    else verify_joint_item<S, 0>(a.ws.pts + i * PROVE_PTS_WORDS, a.T, tabs, c, s);
+  } else {
+    if (blockIdx.y == 0) verify_straus_item<S, 1>(a.ws.pts + i * PROVE_PTS_WORDS + UV_WORDS, a.T, tabs, c, s);
+    else verify_straus_item<S, 0>(a.ws.pts + i * PROVE_PTS_WORDS, a.T, tabs, c, s);
+  }
 }
 
 // stage 3: VERIFY_K proofs per lane share one inversion (2K Z coordinates).  Affine U, V; challenge

@@ -765,6 +765,145 @@ VRF_HD FeN fe_sel3(int p, const FeN& a, const FeN& b, const FeN& c) {
 }
 
 constexpr int VERIFY_TABS = 6;   // Y, psi Y, H, psi H, Gamma, psi Gamma
+
+// the proof's scalars for the ladders: c mod r (upstream decodes `Proof::c` with from_le_bytes_mod_order), s as is;
+// a non-canonical s is reported InvalidData by the finish stage: keep the digits in range here
+template <class S>
+VRF_HD void load_cs_reduced(uint32_t c[8], uint32_t s[8]) {
+  uint32_t cr[8];
+  fr_reduce256<S>(cr, c);
+  const bool s_ok = fr_is_canonical<S>(s);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { c[j] = s_ok ? cr[j] : 0u; s[j] = s_ok ? s[j] : 0u; }
+}
+
+// ---- joint tables: the GLV suite's IETF verifier ----
+// The ladders perform one table addition per 4 scalar bits whatever the tables hold, so the tables are shaped for what they
+// cost to build.  An item's region of VERIFY_TABS * WIN_TABLE_WORDS words holds, as cached entries (PtC):
+//   JT_Y: the 12 sums a*Y + b*psi(Y), (a, b) = (1,0) (2,0) (0,1) (0,2) (1,+-1) (1,+-2) (2,+-1) (2,+-2): every pair of signed
+//         radix-4 digits in {-1, 0, 1, 2} up to a common sign (joint_y_index).  Independent of the proof's scalars.
+//   JT_V: the 15 non-empty subset sums of Q0 = -/+Gamma, Q1 = -/+psi(Gamma), Q2 = +/-H, Q3 = +/-psi(H), each base with the
+//         sign of its GLV half in V = s*H - c*Gamma; entry m - 1 = sum of Q_t over the set bits t of m.
+// and, behind them, what only the decode stage reads: the extended coordinates the next additions start from, and the affine
+// H and Gamma until both are there.
+constexpr int JT_Y_ENTRIES = 12, JT_V_ENTRIES = 15;
+constexpr int JT_Y = 0;
+constexpr int JT_V = JT_Y + JT_Y_ENTRIES * PTC_WORDS;        // word 432
+constexpr int JT_EXT = JT_V + JT_V_ENTRIES * PTC_WORDS;      // word 972: X, Y, Z, T of V entries 1..8 (8 is written, not read)
+constexpr int JT_YEXT = JT_EXT + 8 * PTC_WORDS;              // X, Y, Z, T of Y and 2Y
+constexpr int JT_HXY = JT_YEXT + 2 * PTC_WORDS;              // affine x, y of H
+constexpr int JT_GXY = JT_HXY + 2 * NL;                      // affine x, y of Gamma
+static_assert(JT_GXY + 2 * NL <= VERIFY_TABS * WIN_TABLE_WORDS, "the joint tables and their parking fit the item's region");
+
+VRF_HD void pte_store(uint32_t* m, const PtE& p) {
+  fe_store(m, p.X); fe_store(m + NL, p.Y); fe_store(m + 2 * NL, p.Z); fe_store(m + 3 * NL, p.T);
+}
+VRF_HD PtE pte_load(const uint32_t* m) {
+  PtE p;
+  p.X = fe_load<1, 5>(m); p.Y = fe_load<1, 5>(m + NL); p.Z = fe_load<1, 5>(m + 2 * NL); p.T = fe_load<1, 5>(m + 3 * NL);
+  return p;
+}
+// an affine point waiting for its table: x as the compressed decode leaves it (1, 4), y a product
+VRF_HD void jt_park_xy(uint32_t* m, const Fe<1, 4>& x, const FeN& y) { fe_store(m, x); fe_store(m + NL, y); }
+
+// psi(P) or -psi(P) = psi(-P): the sign rides on the constant c, which only X and T carry (te.cuh te_psi)
+#if VRF_FIELD == 0
+template <class C>
+VRF_HD PtE te_psi_signed(const PtE& p, bool neg) {
+  const FeN b = fe_const(vrfk::BS_PSI_B_M);
+  const auto c = fe_norm(fe_cneg(neg, fe_const(vrfk::BS_PSI_C_M)));       // (1,4)
+  auto YY = fe_sqr(p.Y);
+  auto ZZ = fe_sqr(p.Z);
+  auto XY = fe_mul(p.X, p.Y);
+  auto bZZ = fe_mul(ZZ, b);
+  auto A = fe_sub(ZZ, YY);
+  auto Bv = fe_sub(YY, bZZ);
+  auto Cv = fe_add(YY, bZZ);
+  auto cA = fe_mul(A, c);
+  auto bC = fe_mul(Cv, b);
+  PtE r;
+  r.X = fe_mul(cA, Bv);
+  r.Y = fe_mul(bC, XY);
+  r.Z = fe_mul(XY, Bv);
+  r.T = fe_mul(cA, bC);
+  bool exc = fe_is_zero(r.Z);
+  PtE id = te_identity();
+  r.X = fe_select(exc, id.X, r.X);
+  r.Y = fe_select(exc, id.Y, r.Y);
+  r.Z = fe_select(exc, id.Z, r.Z);
+  r.T = fe_select(exc, id.T, r.T);
+  return r;
+}
+#else
+template <class C>
+VRF_HD PtE te_psi_signed(const PtE& p, bool neg);      // as te_psi: named only in discarded branches
+#endif
+
+// The 12 entries of JT_Y from the affine pk: two doublings, eight additions (one call site each).
+template <class S>
+VRF_HD void build_joint_y_table(uint32_t* reg, const FeP& x, const FeP& y) {
+  const PtE p = te_from_affine(x, y);
+  const PtE q = te_psi<S>(p);
+#pragma unroll 1
+  for (int t = 0; t < 2; ++t) {
+    PtE b;
+    b.X = fe_select(t == 0, p.X, q.X); b.Y = fe_select(t == 0, p.Y, q.Y);
+    b.Z = fe_select(t == 0, p.Z, q.Z); b.T = fe_select(t == 0, p.T, q.T);
+    const PtE d = te_dbl<S>(b, true);
+    ptc_store(reg + JT_Y + 2 * t * PTC_WORDS, te_to_cached<S>(b));
+    ptc_store(reg + JT_Y + (2 * t + 1) * PTC_WORDS, te_to_cached<S>(d));
+    if (t == 0) { pte_store(reg + JT_YEXT, b); pte_store(reg + JT_YEXT + PTC_WORDS, d); }
+  }
+#pragma unroll 1
+  for (int i = 0; i < 8; ++i) {                 // (a, b) = (1 + i / 4, +-(1 + (i / 2) % 2)), odd i: minus
+    const PtE e = pte_load(reg + JT_YEXT + (i >> 2) * PTC_WORDS);
+    const PtC c = ptc_load(reg + JT_Y + (2 + ((i >> 1) & 1)) * PTC_WORDS);
+    ptc_store(reg + JT_Y + (4 + i) * PTC_WORDS, te_to_cached<S>(te_add_cached<S>(e, c, (i & 1) != 0)));
+  }
+}
+// (a, b) in {-2..2}^2 -> 0 for the neutral element or 1 + the JT_Y entry of +-(a*Y + b*psi Y); neg: the entry is subtracted
+VRF_HD int joint_y_index(int a, int b, bool& neg) {
+  neg = a < 0 || (a == 0 && b < 0);
+  if (neg) { a = -a; b = -b; }
+  const int bm = b < 0 ? -b : b;
+  if (a == 0) return bm == 0 ? 0 : 2 + bm;
+  if (bm == 0) return a;
+  return 5 + ((a - 1) << 2) + ((bm - 1) << 1) + (b < 0 ? 1 : 0);
+}
+
+// The 15 entries of JT_V from the parked affine H and Gamma and the proof's scalars (c, s as load_cs_reduced leaves them --
+// exactly what the V ladder decomposes again).  The four bases come first, then entry m = entry (m - 2^hb) + Q_hb with hb
+// the highest set bit of m: 11 additions, one call site; only entries 1..7 are read back in extended form.
+template <class S>
+VRF_HD void build_joint_v_table(uint32_t* reg, const uint32_t c[8], const uint32_t s[8]) {
+  GlvHalf h[4];
+  glv_decompose_bs(h[0], h[1], c);
+  glv_decompose_bs(h[2], h[3], s);
+  const bool neg0 = !h[0].neg, neg1 = !h[1].neg, neg2 = h[2].neg, neg3 = h[3].neg;       // the c terms are subtracted
+#pragma unroll 1
+  for (int p = 0; p < 2; ++p) {                 // p = 0: Gamma -> Q0, Q1; p = 1: H -> Q2, Q3
+    const uint32_t* xy = reg + (p == 0 ? JT_GXY : JT_HXY);
+    const bool nb = p == 0 ? neg0 : neg2, npsi = p == 0 ? neg1 : neg3;
+    const FeN x = fe_mul(fe_cneg(nb, fe_load<1, 4>(xy)), fe_one());       // -x as a product: back to a storage bound
+    const PtE b = te_from_affine(x, fe_load<1, 2>(xy + NL));
+    const PtE q = te_psi_signed<S>(b, nb != npsi);
+    const int m = 1 << (2 * p);
+    ptc_store(reg + JT_V + (m - 1) * PTC_WORDS, te_to_cached<S>(b));
+    ptc_store(reg + JT_V + (2 * m - 1) * PTC_WORDS, te_to_cached<S>(q));
+    pte_store(reg + JT_EXT + (m - 1) * PTC_WORDS, b);
+    pte_store(reg + JT_EXT + (2 * m - 1) * PTC_WORDS, q);
+  }
+#pragma unroll 1
+  for (int m = 3; m < 16; ++m) {
+    if ((m & (m - 1)) == 0) continue;
+    const int top = m >= 8 ? 8 : (m >= 4 ? 4 : 2);
+    const PtE e = te_add_cached<S>(pte_load(reg + JT_EXT + (m - top - 1) * PTC_WORDS),
+                                   ptc_load(reg + JT_V + (top - 1) * PTC_WORDS), false);
+    ptc_store(reg + JT_V + (m - 1) * PTC_WORDS, te_to_cached<S>(e));
+    if (m < 8) pte_store(reg + JT_EXT + (m - 1) * PTC_WORDS, e);
+  }
+}
+
 // tabs: 6 * WIN_TABLE_WORDS words (GLV table pairs of Y, H, Gamma).  Returns validity.
 template <class S>
 VRF_HD bool verify_decode_item(const DevTables& T, const uint32_t pk[8], const uint32_t hh[8],
@@ -801,10 +940,14 @@ constexpr int DEC_SLOT = 4 * NL;            // per point: y | num | den | prefix
 // NP = 3: pk, H, Gamma (table slots 0, 1, 2); NP = 2 (keyed verification: the key's tables are context
 // resident): H, Gamma (pk is not read, slots 1, 2); NP = 2 with SKIP_H (verification from alpha: H came out of
 // hash-to-curve in this call and its tables are already in slot 1): pk, Gamma (slots 0, 2).
-template <class S, int NP = 3, bool SKIP_H = false>
+// JOINT (the GLV suite's IETF verifier): the item's region gets the joint tables instead -- JT_Y from pk, JT_V once H and
+// Gamma of the item are both parked (the loop below meets Gamma first; with SKIP_H, H's affine x, y are already there), from
+// the proof's scalars in c_arr, s_arr.
+template <class S, int NP = 3, bool SKIP_H = false, bool JOINT = false>
 VRF_HD void verify_decode_multi(int K, const DevTables& T, size_t first, size_t n, const uint8_t* pk,
                                 const uint8_t* hh, const uint8_t* gamma, uint32_t* tabs_base,
-                                uint32_t* scratch_base, uint8_t* flags, uint32_t check_mask = 0) {
+                                uint32_t* scratch_base, uint8_t* flags, uint32_t check_mask = 0,
+                                const uint8_t* c_arr = nullptr, const uint8_t* s_arr = nullptr) {
   // scratch: K * 108 words owned by this lane = 3K point slots of 36 words
   uint32_t* scr = scratch_base + first * (3 * DEC_SLOT);
   FeN run = fe_one();
@@ -848,8 +991,23 @@ VRF_HD void verify_decode_multi(int K, const DevTables& T, size_t first, size_t 
       inv = fe_mul(inv, a.den);
       Fe<1, 4> x;
       bool ok = decode_phase_b<S>(x, a, di, T.sq);
-      uint32_t* tab = tabs_base + item * (VERIFY_TABS * WIN_TABLE_WORDS) + p * 2 * WIN_TABLE_WORDS;
-      build_glv_tables<S>(tab, x, a.y);
+      if constexpr (JOINT) {
+        uint32_t* reg = tabs_base + item * (VERIFY_TABS * WIN_TABLE_WORDS);
+        if (p == 0) build_joint_y_table<S>(reg, x, a.y);
+        else jt_park_xy(reg + (p == 1 ? JT_HXY : JT_GXY), x, a.y);
+        if (p == (SKIP_H ? 2 : 1)) {
+          uint32_t c[8], s[8];
+          const uint32_t* wc = reinterpret_cast<const uint32_t*>(c_arr + item * 32);
+          const uint32_t* ws = reinterpret_cast<const uint32_t*>(s_arr + item * 32);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) { c[k] = wc[k]; s[k] = ws[k]; }
+          load_cs_reduced<S>(c, s);
+          build_joint_v_table<S>(reg, c, s);
+        }
+      } else {
+        uint32_t* tab = tabs_base + item * (VERIFY_TABS * WIN_TABLE_WORDS) + p * 2 * WIN_TABLE_WORDS;
+        build_glv_tables<S>(tab, x, a.y);
+      }
       if ((check_mask >> p) & 1u) ok = in_prime_subgroup<S>(fe_mul(x, fe_one()), a.y, T.sq) && ok;    // bit p: pk, H, Gamma
       if (!ok) valid_mask &= ~(1u << (j / NP));
     }
@@ -936,9 +1094,11 @@ VRF_HD void verify_finish_multi(int K, size_t first, size_t n, uint32_t* pts_bas
 // Same stage for callers that hold affine points in memory (arkworks `Affine { x, y }`): x || y as
 // 32-byte little-endian canonical integers, no square roots.  Validity = coordinates < q and the
 // point is on the curve.
-template <class S>
+// JOINT: as in verify_decode_multi; c, s as load_cs_reduced leaves them.
+template <class S, bool JOINT = false>
 VRF_HD bool verify_decode_affine_item(uint32_t enc_out[3][8], const uint32_t (&xy)[3][16], uint32_t* tabs,
-                                      const SqrtTables& T, uint32_t check_mask = 0, bool mont256 = false) {
+                                      const SqrtTables& T, uint32_t check_mask = 0, bool mont256 = false,
+                                      const uint32_t* c = nullptr, const uint32_t* s = nullptr) {
   bool valid = true;
 #pragma unroll 1
   for (int p = 0; p < 3; ++p) {
@@ -954,7 +1114,12 @@ VRF_HD bool verify_decode_affine_item(uint32_t enc_out[3][8], const uint32_t (&x
     FeN x2 = fe_sqr(x), y2 = fe_sqr(y), xyv = fe_mul(x, y);
     auto lhs = te_curve_lhs<S>(x2, y2);
     valid = fe_eq(lhs, fe_mul(fe_mul(fe_sqr(xyv), S::d()), fe_one())) && valid;
-    build_glv_tables<S>(tabs + p * 2 * WIN_TABLE_WORDS, x, y);
+    if constexpr (JOINT) {
+      if (p == 0) build_joint_y_table<S>(tabs, x, y);
+      else jt_park_xy(tabs + (p == 1 ? JT_HXY : JT_GXY), x, y);
+    } else {
+      build_glv_tables<S>(tabs + p * 2 * WIN_TABLE_WORDS, x, y);
+    }
     if ((check_mask >> p) & 1u) valid = in_prime_subgroup<S>(x, y, T) && valid;
     uint32_t e[8];
 #pragma unroll
@@ -967,6 +1132,7 @@ VRF_HD bool verify_decode_affine_item(uint32_t enc_out[3][8], const uint32_t (&x
       if (p == 2) enc_out[2][j] = e[j];
     }
   }
+  if constexpr (JOINT) build_joint_v_table<S>(tabs, c, s);
   return valid;
 }
 
@@ -1026,6 +1192,72 @@ VRF_HD void verify_straus_item(uint32_t* out_uv, const DevTables& T, const uint3
   fe_store(out_uv + NL, r.Y);
   fe_store(out_uv + 2 * NL, r.Z);
   }
+}
+
+// The same two results from the joint tables (GLV suite; build_joint_y_table / build_joint_v_table above).
+// HALF 0: -c*Y by 64 windows of two doublings and one addition: signed radix-4 digits of the two halves, each with its half's
+//         sign (negated: the term is subtracted), the pair normalised to a JT_Y entry and one negation flag; then s*G from
+//         the fixed-base table, so the last addition keeps T.
+// HALF 1: V bit by bit, 126..0: one doubling (with T: an addition follows) and one addition (without: a doubling follows, or
+//         nothing reads it) of the JT_V entry the four magnitudes' bits select; entry 0 is the neutral element.  The first
+//         bit is a plain load.  Bit 127 of a half is never set (fr.cuh GLV_HALF_TOP_WORD_CAP).
+template <class S>
+VRF_HD PtE joint_u_ladder(const uint32_t* ytab, const GlvHalf& c1, const GlvHalf& c2) {
+  uint32_t r1[4], r2[4];
+  scalar_recode_signed2_128(r1, c1.mag);
+  scalar_recode_signed2_128(r2, c2.mag);
+  const bool n1 = !c1.neg, n2 = !c2.neg;
+  PtE acc = te_identity();
+#pragma unroll 1
+  for (int w = 63; w >= 0; --w) {
+    if (w != 63) {
+#pragma unroll 1
+      for (int j = 0; j < 2; ++j) acc = te_dbl<S, true>(acc, j == 1);
+    }
+    const int d1 = scalar_digit2_128(r1, w), d2 = scalar_digit2_128(r2, w);
+    bool neg;
+    const int idx = joint_y_index(n1 ? -d1 : d1, n2 ? -d2 : d2, neg);
+    acc = te_add_cached<S, true>(acc, win_lookup(ytab, idx), neg, w == 0);
+  }
+  return acc;
+}
+VRF_HD int joint_v_index(const uint32_t (&m)[4][4], int bit) {
+  return scalar_bit_128(m[0], bit) | (scalar_bit_128(m[1], bit) << 1) | (scalar_bit_128(m[2], bit) << 2) |
+         (scalar_bit_128(m[3], bit) << 3);
+}
+template <class S>
+VRF_HD PtE joint_v_ladder(const uint32_t* vtab, const uint32_t (&m)[4][4]) {
+  const PtC first = win_lookup(vtab, joint_v_index(m, 126));
+  PtE acc;
+  acc.X = first.X; acc.Y = first.Y; acc.Z = first.Z; acc.T = fe_zero();
+#pragma unroll 1
+  for (int bit = 125; bit >= 0; --bit) {
+    acc = te_dbl<S, true>(acc, true);
+    acc = te_add_cached<S, true>(acc, win_lookup(vtab, joint_v_index(m, bit)), false, false);
+  }
+  return acc;
+}
+template <class S, int HALF>
+VRF_HD void verify_joint_item(uint32_t* out_uv, const DevTables& T, const uint32_t* reg, const uint32_t c[8],
+                              const uint32_t s[8]) {
+  GlvHalf h[4];
+  glv_decompose_bs(h[0], h[1], c);
+  PtE r;
+  if (HALF == 0) {
+    r = joint_u_ladder<S>(reg + JT_Y, h[0], h[1]);
+    r = gcomb_add<S, true>(r, T.g_comb, s);
+  } else {
+    glv_decompose_bs(h[2], h[3], s);
+    uint32_t m[4][4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) m[t][i] = h[t].mag[i];
+    r = joint_v_ladder<S>(reg + JT_V, m);
+  }
+  fe_store(out_uv, r.X);
+  fe_store(out_uv + NL, r.Y);
+  fe_store(out_uv + 2 * NL, r.Z);
 }
 
 template <class S>
