@@ -60,6 +60,9 @@ using namespace vrf;
 // divsteps loop (~18 k instructions) the extra waves of a small K are worth more than the shared inversion: measured at
 // 2^20, IETF verify 40.3 (K = 8) / 39.7 ms (K = 2), the batched Pedersen decode on JubJub 22.1 / 20.7 ms.
 constexpr int VERIFY_K_POLICY = 2;
+// The IETF verifiers' decode launches share nothing across a lane's proofs (every point is decompressed by its own inverse
+// root), so their proofs per lane is a matter of grid size alone.
+constexpr int VERIFY_K_DECODE = 1;
 
 namespace {
 
@@ -839,6 +842,7 @@ int32_t verify_dev_impl(vrfhip_ctx* ctx, size_t n, bool affine, const uint8_t* d
     common(a);
     a.suite = (int)ctx->suite;
     a.k_lane = lanes_k(m, VERIFY_K_POLICY);
+    a.k_decode = VERIFY_K_DECODE < a.k_lane ? VERIFY_K_DECODE : a.k_lane;
     if (ks) a.pk = ks->d_enc;                 // the key set's encodings, not a per-proof array
     a.check_mask = ctx->check_mask();
     a.ws = ctx->ws;
@@ -979,6 +983,7 @@ int32_t vrfhip_ietf_verify_batch_alpha_dev(vrfhip_ctx* ctx, size_t n, const uint
       FIELD_CALL(ctx, launch_verify_input_from_alpha((int)ctx->suite, m, mv, d_henc, ctx->ws.tabs, ctx->T, st, ctx->ws.flags,
                                                      ctx->d_queue));
       a.k_lane = lanes_k(m, VERIFY_K_POLICY);
+      a.k_decode = VERIFY_K_DECODE < a.k_lane ? VERIFY_K_DECODE : a.k_lane;
       a.h_in_tabs = 1;
       FIELD_CALL(ctx, launch_ietf_verify(a, st, prof_events(ctx)));
     }

@@ -583,7 +583,10 @@ VRF_HD bool limbs_eq(const FeN& a, const uint32_t (&c)[NL]) {
   return o == 0;
 }
 
-// root = w^((t+1)/2) h^(e/2) (e even) or sqrt(Z w) = Z^((t+1)/2) w^((t+1)/2) h^((e+1)/2) (e odd); returns e even
+// root = w^((t+1)/2) h^(e/2) (e even) or sqrt(Z w) = Z^((t+1)/2) w^((t+1)/2) h^((e+1)/2) (e odd); returns e even.
+// INV: x0 is w^((t-1)/2) instead, and root = w^((t-1)/2) h^(e/2) = 1 / sqrt(w) for e even (the product with the line
+// above is w^t h^e = 1); for e odd it is left as that product stands, which no caller reads.
+template <bool INV>
 VRF_HD bool sqrt_finish(FeN& root, const FeN& x0, uint32_t e, const SqrtTables& T) {
   bool odd = e & 1;
   uint32_t half = (e >> 1) + (e & 1);               // in [0, 2^31]
@@ -591,18 +594,24 @@ VRF_HD bool sqrt_finish(FeN& root, const FeN& x0, uint32_t e, const SqrtTables& 
   r = fe_mul(r, sqrt_tbl(T, 1, (half >> 8) & 255));
   r = fe_mul(r, sqrt_tbl(T, 2, (half >> 16) & 255));
   r = fe_mul(r, sqrt_tbl(T, 3, half >> 24));
-  FeN rz = fe_mul(r, fe_const(vrfk::SQRT_CZ_M));
-  root = fe_select(odd, rz, r);
+  if constexpr (INV) {
+    root = r;
+  } else {
+    FeN rz = fe_mul(r, fe_const(vrfk::SQRT_CZ_M));
+    root = fe_select(odd, rz, r);
+  }
   return !odd;    // w == 0: b = 0, lut garbage, but x0 = 0 => root = 0; caller treats 0 as square
 }
 
-template <int L, int V>
-VRF_HD bool fe_sqrt_or_zsqrt(FeN& root, const Fe<L, V>& w_in, const SqrtTables& T) {
-  FeN w = fe_mul(w_in, fe_one());
+// The walk behind fe_sqrt_or_zsqrt and fe_inv_sqrt (INV) below, on a normalised w.
+template <bool INV>
+VRF_HD bool fe_sqrt_walk(FeN& root, const FeN& w, const SqrtTables& T) {
   FeN v = fe_pow_prog(w, vrfk::POW_SQRT_PROG);        // w^((t-1)/2)
   FeN x0 = fe_mul(w, v);                            // w^((t+1)/2)
   FeN b = fe_mul(x0, v);                            // w^t, in the 2^S-torsion
+  const FeN base = INV ? v : x0;
   if constexpr (vrfk::SQRT_S == 1) {
+    static_assert(!INV, "no inverse root where the exponentiation is the root");
     // q = 3 (mod 4), Z = -1: x0 = w^((q+1)/4) squares to w chi(w), i.e. it is sqrt(w) or sqrt(Z w) as it stands
     root = x0;
     const FeN bc = fe_canon(b);                       // chi(w): 1, -1 or 0
@@ -619,9 +628,13 @@ VRF_HD bool fe_sqrt_or_zsqrt(FeN& root, const Fe<L, V>& w_in, const SqrtTables& 
     const bool odd = e & 1;
     const uint32_t half = (e >> 1) + (e & 1);       // 0, 1, 1, 2
     const FeN hm = fe_select(half == 0, fe_one(), fe_select(half == 1, fe_const(vrfk::SQRT_H1_M), fe_const(vrfk::SQRT_H2_M)));
-    FeN r = fe_mul(x0, hm);
-    FeN rz = fe_mul(r, fe_const(vrfk::SQRT_CZ_M));
-    root = fe_select(odd, rz, r);
+    FeN r = fe_mul(base, hm);
+    if constexpr (INV) {
+      root = r;
+    } else {
+      FeN rz = fe_mul(r, fe_const(vrfk::SQRT_CZ_M));
+      root = fe_select(odd, rz, r);
+    }
     return !odd;
 #endif
   } else if constexpr (vrfk::SQRT_S == 28) {
@@ -637,7 +650,7 @@ VRF_HD bool fe_sqrt_or_zsqrt(FeN& root, const Fe<L, V>& w_in, const SqrtTables& 
     uint32_t e2 = sqrt_lut_index(T, fe_mul(fe_mul(b4, sqrt_tbl(T, 4, e0)), sqrt_tbl(T, 5, e1)));
     uint32_t e3 = sqrt_lut_index(
         T, fe_mul(fe_mul(fe_mul(b, sqrt_tbl(T, 0, e0)), sqrt_tbl(T, 1, e1)), sqrt_tbl(T, 2, e2))) >> 4;
-    return sqrt_finish(root, x0, e0 | (e1 << 8) | (e2 << 16) | (e3 << 24), T);
+    return sqrt_finish<INV>(root, base, e0 | (e1 << 8) | (e2 << 16) | (e3 << 24), T);
   } else {
     static_assert(vrfk::SQRT_S <= 2 || vrfk::SQRT_S == 28 || vrfk::SQRT_S == 32, "no square-root plan for this 2-adicity");
     FeN b8 = b;
@@ -652,9 +665,23 @@ VRF_HD bool fe_sqrt_or_zsqrt(FeN& root, const Fe<L, V>& w_in, const SqrtTables& 
     uint32_t e2 = sqrt_lut_index(T, fe_mul(fe_mul(b8, sqrt_tbl(T, 1, e0)), sqrt_tbl(T, 2, e1)));
     uint32_t e3 = sqrt_lut_index(
         T, fe_mul(fe_mul(fe_mul(b, sqrt_tbl(T, 0, e0)), sqrt_tbl(T, 1, e1)), sqrt_tbl(T, 2, e2)));
-    return sqrt_finish(root, x0, e0 | (e1 << 8) | (e2 << 16) | (e3 << 24), T);
+    return sqrt_finish<INV>(root, base, e0 | (e1 << 8) | (e2 << 16) | (e3 << 24), T);
   }
 }
+
+template <int L, int V>
+VRF_HD bool fe_sqrt_or_zsqrt(FeN& root, const Fe<L, V>& w_in, const SqrtTables& T) {
+  return fe_sqrt_walk<false>(root, fe_mul(w_in, fe_one()), T);
+}
+
+// 1 / sqrt(w) from the same exponentiation, the same discrete-logarithm walk and the same four table products: with
+// v = w^((t-1)/2), x0 = w v and x0 v = w^t = g^e, sqrt(w) = x0 h^(e/2) and 1 / sqrt(w) = v h^(e/2).  Returns
+// is_square(w) and sets `root` to the inverse root if w is a non-zero square and to 0 if w = 0 (v = 0; the caller treats
+// 0 as a square, as with fe_sqrt_or_zsqrt); for a non-square w `root` is not a root of anything.  For the fields whose
+// 2-adicity has a table plan or the four constants (S = 32, 28, 2).  Constant shape.
+#if VRF_FIELD != 3
+VRF_HD bool fe_inv_sqrt(FeN& root, const FeN& w, const SqrtTables& T) { return fe_sqrt_walk<true>(root, w, T); }
+#endif
 
 
 // Low byte of the 2-adic discrete logarithm: w = (odd-order part) * g^e with g the generator of the
@@ -681,20 +708,47 @@ VRF_HD uint32_t fe_dlog2_low8(const Fe<L, V>& w_in, const SqrtTables& T) {
 // and g and the counter eta only, so a round of JAC_K = 29 steps runs on the low 32-bit words (one VGPR each) and
 // yields a 2x2 matrix of non-negative entries, each row summing to at most 2^29 (every step doubles the f row and
 // adds it to the g row at most once); applying it to the 9-limb numbers divides by 2^29 exactly, i.e. drops one
-// 29-bit limb, and the 64-bit column sums stay below 2 * 2^29 * 2^29 + carry < 2^60.  24..30 rounds for 255-bit
-// inputs (measured on 3e4 random values; a wave pays the maximum of its lanes, ~29).
-// The steps of a round run several at a time (jac_steps_var, libsecp256k1's variable-time "posdivsteps"): all
-// trailing zeros of g in one shift, then, with g odd and eta >= 0 after the swap, up to min(eta + 1, steps left, 4)
-// low bits of g cleared at once by g += f w, w = -g / f (mod 2^k).  eta + 1 bounds k because no swap can come
-// before eta turns negative, so the batch is the single steps' own sequence and the matrix, the sign and eta come
-// out identical.  ~9 iterations per lane and round, ~13 for the slowest lane of a wave of random inputs, against
-// 29 single steps, the 36 multiply-adds of the matrix product unchanged: 11 % fewer VALU instructions and 8 % less
-// time in the checked verify decode kernel (six symbols and half an inversion per proof), measured on MI355X.
+// 29-bit limb, and the 64-bit column sums stay below 2 * 2^29 * 2^29 + carry < 2^60.
+// The steps run several at a time (libsecp256k1's variable-time "posdivsteps"): all trailing zeros of g in one shift,
+// then, with g odd and eta >= 0 after the swap, up to min(eta + 1, steps left, 4) low bits of g cleared at once by
+// g += f w, w = -g / f (mod 2^k).  eta + 1 bounds k because no swap can come before eta turns negative, so the batch is
+// the single steps' own sequence and the matrix, the sign and eta come out identical.
+// Rounds are paced evenly (jac_steps_paced): a round is JAC_NITER such trips, the same for every lane, and takes the
+// s <= 29 steps those trips give the lane; its matrix is scaled by 2^(29 - s), so the column code still drops one limb
+// exactly and the lane has divided by 2^s.  The divsteps sequence, the sign and eta are the single steps' own, cut at
+// other places.  Running exactly 29 steps per round instead cost a wave the trips of its slowest lane in every round
+// (~13 against ~9 for a lane, a third of the loop under a partly empty mask); a lane's total trips average out over
+// its ~30 rounds, so the wave's maximum of whole rounds is 12 % above the lane's mean where the maximum of trips was 44 %.
+// JAC_NITER = 8, from the compiled loop on gfx950 (36 VALU per unrolled trip, ~160 per round for the matrix product,
+// the final shift and the bookkeeping; the parent's divergent trip ~45 slots with its mask handling) and the rounds a
+// wave of 64 random inputs below q needs (300 waves; lane mean / wave maximum):
+//     NITER   rounds         slots per symbol and wave
+//     7       30.6 / 34.9    14.4 k
+//     8       28.2 / 31.6    14.2 k        (29 steps, wave-maximum trips: 28.2 / 29, 21 k)
+//     9       27.0 / 29.7    14.4 k
+//     10      26.5 / 28.8    15.0 k
+// JAC_VAR_ROUNDS: every trip of a running lane takes at least one step, and a single step (eta = 0, k = 1) leaves
+// eta = -1, so the next trip swaps and takes at least two: a round is worth >= 12 steps however the input was chosen, and
+// inputs that keep eta small ride the cycle of two steps per trip.  Random inputs need <= 36 rounds (1.2e5 samples per
+// field, the tail falls ~5x per round); 2^k, q - 2^k, values with long runs of low zeros and the Montgomery images of
+// 1, 2, q - 1 need up to 48.  The cap is 62, as far as fe_inv's value bound lets it go; a lane beyond it takes the
+// exponentiation, as before.  The symbol also keeps the step budget of 40 rounds of 29 (JAC_STEP_BUDGET), so that it gives
+// up exactly where it did (tests/test_divsteps.py pins that set): q - 2, q - 2^21 of 2^255 - 19 are such inputs.
 // chi(R) = chi(2)^261 = 1 because q = 1 (mod 8) for both Montgomery fields (and R = 1 for 2^255 - 19): the symbol of
 // the stored image is the symbol of the value.
 static_assert(vrfk::CHI_R == 1, "jacobi_limbs callers assume chi(R) = 1");
 constexpr int JAC_K = 29;
-constexpr int JAC_MAX_ROUNDS = 40;      // rounds needed: <= 30 in 3e4 samples, tail decays ~50x per round
+constexpr int JAC_MAX_ROUNDS = 40;      // the prover's fixed count of full 29-step rounds (jac_steps_ct): <= 30 needed in 3e4 samples
+#ifndef VRF_JAC_NITER
+#define VRF_JAC_NITER 8
+#endif
+constexpr int JAC_NITER = VRF_JAC_NITER;   // trips of an evenly paced round (the table above; -DVRF_JAC_NITER=7, 9 built the kernels timed beside it: DESIGN.md section 4)
+constexpr int JAC_VAR_ROUNDS = 62;      // cap of the evenly paced rounds (above)
+// A compatibility constraint, not a need of the algorithm: the symbol gives up on the inputs it gave up on with rounds of
+// 29 steps, i.e. once the 40 * 29 steps of those are spent, because tests/test_divsteps.py pins that set with its model of
+// single steps.  Without it the cap of 62 rounds would answer some of them (q - 2^21 of 2^255 - 19 in 58 rounds).
+constexpr int JAC_STEP_BUDGET = JAC_K * JAC_MAX_ROUNDS;
+static_assert(JAC_VAR_ROUNDS + 1 < 64, "fe_inv: d < (rounds + 1) q must stay inside the value bound of its result");
 static_assert(JAC_K + 3 <= 32, "after JAC_K steps the low words must still hold the bits 1 and 2 that the sign reads");
 
 // wave-level "any lane" on the device, identity on the host build
@@ -727,55 +781,81 @@ VRF_HD int32_t jac_steps_ct(int32_t eta, uint32_t f, uint32_t g, JacTrans& t) {
   return eta;
 }
 
-// `left` steps (JAC_K, or 0 for a lane that idles) several at a time, as described above; returns eta.  SIGN: bit 1
-// of `jac` follows the sign of the symbol.  The trip count varies per lane; a finished lane waits under the mask.
-// Every partial matrix is the single steps' matrix at some step, so no entry exceeds 2^JAC_K: u w and v w are the
-// f row after k more doublings and fit 32 bits like the rest.
+// One evenly paced round: JAC_NITER trips of the variable-time batch above, or fewer once `left` steps (JAC_K, or 0 for a
+// lane that idles) are used up, then the trailing zeros of g that the steps left still cover.  Returns the steps taken,
+// s <= left; eta is updated in place.  SIGN: bit 1 of `jac` follows the sign of the symbol.  The trip count is the same
+// for every lane, so the loop unrolls and no lane waits under the mask for the slowest of its wave; a lane out of steps
+// (i = 0) is inert in a trip: the sentinel makes z = 0, it does not swap, and k = 0 makes w = 0.
+// Every partial matrix is the single steps' matrix at some step, so no entry exceeds 2^s: u w and v w are the f row after
+// k more doublings and fit 32 bits like the rest.
 template <bool SIGN>
-VRF_HD int32_t jac_steps_var(int32_t eta, uint32_t f, uint32_t g, int left, JacTrans& t, uint32_t& jac) {
+VRF_HD int jac_steps_paced(int32_t& eta_io, uint32_t f, uint32_t g, int left, JacTrans& t, uint32_t& jac) {
   uint32_t u = 1, v = 0, q = 0, r = 1;
+  int32_t eta = eta_io;
   int i = left;
-#pragma unroll 1
-  for (;;) {
+#pragma unroll
+  for (int trip = 0; trip <= JAC_NITER; ++trip) {
     const int z = __builtin_ctz(g | (~0u << i));             // steps with g even, at most the i left (sentinel bit)
     g >>= z; u <<= z; v <<= z; eta -= z; i -= z;
     if (SIGN) jac ^= (f ^ (f >> 1)) & ((uint32_t)z << 1);  // (2 / f)^z: -1 iff f = 3, 5 (mod 8) and z odd
-    if (i == 0) break;
-    const bool sw = eta < 0;                                 // g odd: swap if eta < 0
+    if (trip == JAC_NITER) break;                            // the last pass only takes the zeros the last trip made
+    const bool sw = i != 0 && eta < 0;                       // g odd: swap if eta < 0
     if (SIGN) jac ^= sw ? f & g : 0u;
     const uint32_t nf = sw ? g : f, ng = sw ? f : g, nu = sw ? q : u, nq = sw ? u : q, nv = sw ? r : v, nr = sw ? v : r;
     f = nf; g = ng; u = nu; q = nq; v = nv; r = nr;
     eta = sw ? -eta : eta;
-    int k = eta + 1 < i ? eta + 1 : i;
-    k = k < 4 ? k : 4;
+    // k = min(eta + 1, i, 4); a lane with i = 0 may hold eta < -1, which the unsigned minimum turns into k = 0 as well
+    uint32_t k = (uint32_t)(eta + 1) < (uint32_t)i ? (uint32_t)(eta + 1) : (uint32_t)i;
+    k = k < 4u ? k : 4u;
     // w = -g / f (mod 2^k): f (f^2 - 2) = -1 / f (mod 16); the operands are cut to 4 bits so the products are 24-bit ones
     const uint32_t f4 = f & 15u, g4 = g & 15u;
     const uint32_t w = (g4 * f4 * ((f4 * f4 + 14u) & 15u)) & ((1u << k) - 1u);
     g += f * w; q += u * w; r += v * w;                      // clears the k low bits of g; the next shift takes them
   }
-  t = JacTrans{u, v, q, r};
-  return eta;
+  // s = left - i steps were taken: scale by 2^(JAC_K - s) so that the callers' exact division by 2^JAC_K divides by 2^s,
+  // (2^(K-s) u f + 2^(K-s) v g) / 2^K = (u f + v g) / 2^s.  Entries and row sums stay <= 2^JAC_K.
+  const int pad = JAC_K - (left - i);
+  t = JacTrans{u << pad, v << pad, q << pad, r << pad};
+  eta_io = eta;
+  return left - i;
 }
 
-// x: exact 29-bit limbs of an integer in [0, 2^256).  Returns +1 / -1, 0 if x = 0 (mod q), 2 if the rounds ran out.
-VRF_HD int jacobi_limbs(const uint32_t x[NL]) {
-  uint32_t f[NL], g[NL];
-  uint32_t nz = 0, dq = 0;
+// x: exact 29-bit limbs of an integer in [0, 2q), below 2^256.  Returns +1 / -1, 0 if x = 0 (mod q), 2 if the lane gave up:
+// f = 1 not seen at the end of a round within JAC_STEP_BUDGET steps or JAC_VAR_ROUNDS rounds.
+VRF_HD int jacobi_limbs(const uint32_t x[NL], int* rounds_out = nullptr) {
+  uint32_t f[NL], g[NL], d[NL];
+  // inputs are < 2q; one in [q, 2q) goes in as x - q (this replaces the test x == q: callers pass fe_canon's [0, q)): the rounds pace themselves on values below f (q + 1 as it stands
+  // would ride the slow cycle for 83 rounds where q = 2^255 - 19)
+  uint32_t borrow = 0;
 #pragma unroll
-  for (int i = 0; i < NL; ++i) { f[i] = vrfk::Q29[i]; g[i] = x[i]; nz |= x[i]; dq |= x[i] ^ vrfk::Q29[i]; }
-  const bool zero = nz == 0 || dq == 0;          // canonical inputs are < 2q: the multiples of q are 0 and q
+  for (int i = 0; i < NL; ++i) {
+    const uint32_t t = x[i] - vrfk::Q29[i] - borrow;
+    borrow = t >> 31;
+    d[i] = (i < NL - 1) ? (t & LMASK) : t;
+  }
+  uint32_t nz = 0;
+#pragma unroll
+  for (int i = 0; i < NL; ++i) { f[i] = vrfk::Q29[i]; g[i] = borrow ? x[i] : d[i]; nz |= g[i]; }
+  const bool zero = nz == 0;
   int32_t eta = -1;
   uint32_t jac = 0;                               // bit 1 carries the sign
   bool done = zero;
+  int rounds = 0, steps = 0;
 #pragma unroll 1
-  for (int round = 0; round < JAC_MAX_ROUNDS; ++round) {
-    if (!vrf_any(!done)) break;
+  for (int round = 0; round < JAC_VAR_ROUNDS; ++round) {
+    const bool idle = done || steps >= JAC_STEP_BUDGET;       // finished, or given up
+    if (!vrf_any(!idle)) break;
+    rounds += idle ? 0 : 1;
     const uint32_t f0 = f[0] | (f[1] << LW), g0 = g[0] | (g[1] << LW);
     uint32_t jl = jac;
     JacTrans t;
-    const int32_t e = jac_steps_var<true>(eta, f0, g0, done ? 0 : JAC_K, t, jl);
+    int32_t e = eta;
+    // the last round stops at the budget, where the rounds of 29 steps looked at f for the last time
+    const int room = JAC_STEP_BUDGET - steps;
+    steps += jac_steps_paced<true>(e, f0, g0, idle ? 0 : (room < JAC_K ? room : JAC_K), t, jl);
     const uint32_t u = t.u, v = t.v, q = t.q, r = t.r;
-    // (f, g) <- (u f + v g, q f + r g) / 2^29: the low limb of both sums is zero by construction
+    // (f, g) <- (u f + v g, q f + r g) / 2^29, the matrix scaled so that this is the round's 2^s: the low limb of both
+    // sums is zero by construction
     uint32_t nf[NL], ng[NL];
     uint64_t af = mad(u, f[0], (uint64_t)v * g[0]) >> LW, ag = mad(q, f[0], (uint64_t)r * g[0]) >> LW;
 #pragma unroll
@@ -792,11 +872,12 @@ VRF_HD int jacobi_limbs(const uint32_t x[NL]) {
     const bool now_one = nf[0] == 1u && rest == 0;
     // lanes that had finished keep their state (f = 1 is not absorbing under further steps)
 #pragma unroll
-    for (int i = 0; i < NL; ++i) { f[i] = done ? f[i] : nf[i]; g[i] = done ? g[i] : ng[i]; }
-    eta = done ? eta : e;
-    jac = done ? jac : jl;
-    done = done || now_one;
+    for (int i = 0; i < NL; ++i) { f[i] = idle ? f[i] : nf[i]; g[i] = idle ? g[i] : ng[i]; }
+    eta = idle ? eta : e;
+    jac = idle ? jac : jl;
+    done = done || (!idle && now_one);
   }
+  if (rounds_out) *rounds_out = rounds;
   if (zero) return 0;
   if (!done) return 2;
   return (jac & 2u) ? -1 : 1;
@@ -831,15 +912,15 @@ VRF_HD bool fe_is_square_or_zero(const Fe<L, V>& w, const SqrtTables& T) {
 // image a~, and f = d a~, g = e a~ (mod q) throughout.  The round's 2x2 matrix (entries <= 2^29, rows summing to at most
 // 2^29) is applied to (f, g) -- an exact division by 2^29 -- and to (d, e), where the multiple of q that makes the division
 // exact is (low limb) * (-q^-1 mod 2^29): -(low limb) when q = 1 (mod 2^29).  f = 1 ends a lane with d = a~^-1 < (rounds + 1) q:
-// each round maps d, e < k q to u d + v e + md q < (2^29 k + 2^29) q / 2^29 = (k + 1) q.  About 27 rounds; the steps of a
-// round run several at a time (jac_steps_var), ~13 iterations for a wave against 29 single steps, with the matrix product
-// unchanged: ~11 % fewer VALU instructions in the verify finish kernel, whose main cost this is.  Against 255 squarings +
-// 30 products (~60 k) for a^(q-2).  0 -> 0, as the power gives.
+// each round maps d, e < k q to u d + v e + md q < (2^29 k + 2^29) q / 2^29 = (k + 1) q.  The rounds are the evenly
+// paced ones of the symbol (jac_steps_paced: eight trips, s <= 29 steps, the matrix scaled by 2^(29 - s), so that (d, e)
+// are divided by 2^s like (f, g)): ~28 for a lane, ~32 for a wave; row sums stay <= 2^29, so the bound on d holds with the
+// rounds counted as they are now.  Against 255 squarings + 30 products (~60 k) for a^(q-2).  0 -> 0, as the power gives.
 // CT = true (the prover's inversions: the Z coordinates of sk*H, k*H, k*G depend on secrets): every lane runs all
 // JAC_MAX_ROUNDS rounds of 29 single steps (jac_steps_ct), so the time no longer follows the operand.
-// Verification and decoding invert public data and keep the early exit (~27 rounds instead of 40) and the variable steps.
+// Verification and decoding invert public data and keep the early exit and the variable steps.
 template <bool CT = false, int L, int V>
-VRF_HD FeN fe_inv(const Fe<L, V>& a) {
+VRF_HD FeN fe_inv(const Fe<L, V>& a, int* rounds_out = nullptr) {
   const FeN c = fe_canon(a);
   uint32_t f[NL], g[NL], d[NL], e[NL];
   uint32_t nz = 0;
@@ -847,17 +928,19 @@ VRF_HD FeN fe_inv(const Fe<L, V>& a) {
   for (int i = 0; i < NL; ++i) { f[i] = vrfk::Q29[i]; g[i] = c.v[i]; d[i] = 0; e[i] = (i == 0); nz |= c.v[i]; }
   int32_t eta = -1;
   bool done = nz == 0;
+  int rounds = 0;
 #pragma unroll 1
-  for (int round = 0; round < JAC_MAX_ROUNDS; ++round) {
+  for (int round = 0; round < (CT ? JAC_MAX_ROUNDS : JAC_VAR_ROUNDS); ++round) {
     if (!CT && !vrf_any(!done)) break;
+    rounds += done ? 0 : 1;
     const uint32_t f0 = f[0] | (f[1] << LW), g0 = g[0] | (g[1] << LW);
     JacTrans t;
-    int32_t et;
+    int32_t et = eta;
     if constexpr (CT) {
       et = jac_steps_ct(eta, f0, g0, t);
     } else {
       uint32_t no_sign = 0;
-      et = jac_steps_var<false>(eta, f0, g0, done ? 0 : JAC_K, t, no_sign);
+      jac_steps_paced<false>(et, f0, g0, done ? 0 : JAC_K, t, no_sign);
     }
     const uint32_t u = t.u, v = t.v, q = t.q, r = t.r;
     uint32_t nf[NL], ng[NL], nd[NL], ne[NL];
@@ -890,13 +973,14 @@ VRF_HD FeN fe_inv(const Fe<L, V>& a) {
     eta = done ? eta : et;
     done = done || now_one;
   }
+  if (rounds_out) *rounds_out = done ? rounds : -1;
   if (vrf_any(!done)) {                       // rounds exhausted (not observed): the power, for the whole wave
     const FeN slow = fe_inv_pow(a);
     if (!done) return slow;
   }
-  // d < (JAC_MAX_ROUNDS + 1) q = 41 q.  A 256-bit q (P-256, VMAX = 32) puts that above the typed range: there the top
+  // d < (JAC_VAR_ROUNDS + 1) q = 63 q.  A 256-bit q (P-256, VMAX = 32) puts that above the typed range: there the top
   // limb is < 2^30 (declared as L = 2) and the first product below is by the constant R^2 mod q < q, so its value is
-  // < q (1 + 41 q / R) < 2.3 q, inside what mul_v(32, 2) = 3 claims for it.
+  // < q (1 + 63 q / R) < 2.97 q, inside what mul_v(32, 2) = 3 claims for it.
   Fe<(vrfk::VMAX < 64 ? 2 : 1), (vrfk::VMAX < 64 ? vrfk::VMAX : 64)> dd;
 #pragma unroll
   for (int i = 0; i < NL; ++i) dd.v[i] = nz == 0 ? 0u : d[i];

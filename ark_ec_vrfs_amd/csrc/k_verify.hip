@@ -9,12 +9,12 @@ VRF_NS_BEGIN
 
 // stage 1: one lane per proof.  Decompress pk, H, Gamma; build their window tables -- the GLV suite: the joint tables of
 // -c*Y and of V = s*H - c*Gamma (vrf_core.cuh JT_Y, JT_V; the latter takes the proof's c and s), the other suites: one
-// radix-16 table per point.  VERIFY_K proofs per lane share one inversion (3K decompression denominators).
+// radix-16 table per point.  A lane's proofs (a.k_decode of them) share nothing: every point has its own inverse root.
 template <class S, int MINW>
 __global__ void __launch_bounds__(BLOCK, MINW) k_verify_decode(VerifyArgs a) {
-  size_t first = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * a.k_lane;
+  size_t first = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * a.k_decode;
   if (first >= a.n) return;
-  verify_decode_multi<S, 3, false, S::HAS_GLV>(a.k_lane, a.T, first, a.n, a.pk, a.h, a.gamma, a.ws.tabs, a.ws.pts, a.ws.flags,
+  verify_decode_multi<S, 3, false, S::HAS_GLV>(a.k_decode, a.T, first, a.n, a.pk, a.h, a.gamma, a.ws.tabs, a.ws.pts, a.ws.flags,
                                                a.check_mask, a.c, a.s);
 }
 
@@ -42,21 +42,21 @@ __global__ void __launch_bounds__(BLOCK, 2) k_verify_input_from_alpha(size_t n, 
 // stage 1 after it: pk and Gamma only
 template <class S, int MINW>
 __global__ void __launch_bounds__(BLOCK, MINW) k_verify_decode_skip_h(VerifyArgs a) {
-  size_t first = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * a.k_lane;
+  size_t first = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * a.k_decode;
   if (first >= a.n) return;
-  verify_decode_multi<S, 2, true, S::HAS_GLV>(a.k_lane, a.T, first, a.n, a.pk, nullptr, a.gamma, a.ws.tabs, a.ws.pts,
+  verify_decode_multi<S, 2, true, S::HAS_GLV>(a.k_decode, a.T, first, a.n, a.pk, nullptr, a.gamma, a.ws.tabs, a.ws.pts,
                                               a.ws.flags, a.check_mask, a.c, a.s);
 }
 
 // stage 1, keyed: only H and Gamma are decompressed; validity also requires a valid, existing key
 template <class S, int MINW>
 __global__ void __launch_bounds__(BLOCK, MINW) k_verify_decode_keyed(VerifyArgs a) {
-  size_t first = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * a.k_lane;
+  size_t first = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * a.k_decode;
   if (first >= a.n) return;
-  verify_decode_multi<S, 2, false, S::HAS_GLV>(a.k_lane, a.T, first, a.n, nullptr, a.h, a.gamma, a.ws.tabs, a.ws.pts,
+  verify_decode_multi<S, 2, false, S::HAS_GLV>(a.k_decode, a.T, first, a.n, nullptr, a.h, a.gamma, a.ws.tabs, a.ws.pts,
                                                a.ws.flags, a.check_mask, a.c, a.s);
 #pragma unroll 1
-  for (int k = 0; k < a.k_lane; ++k) {
+  for (int k = 0; k < a.k_decode; ++k) {
     const size_t i = first + k;
     if (i >= a.n) break;
     const uint32_t key = a.key_index[i];
@@ -150,14 +150,18 @@ __global__ void __launch_bounds__(BLOCK, MINW) k_verify_finish(VerifyArgs a) {
 }
 
 template <class S>
-static void launch_verify_t(const VerifyArgs& a, hipStream_t st, hipEvent_t* ev) {
+static void launch_verify_t(const VerifyArgs& a_in, hipStream_t st, hipEvent_t* ev) {
+  VerifyArgs a = a_in;
+  if (a.k_decode <= 0) a.k_decode = a.k_lane;
   const size_t lanes_k_ = (a.n + a.k_lane - 1) / a.k_lane;      // K proofs per lane: a small grid
   const dim3 gk = grid_for(lanes_k_);
+  const size_t lanes_d = (a.n + a.k_decode - 1) / a.k_decode;   // the decode launches' own K
+  const dim3 gd = grid_for(lanes_d);
   if (ev) (void)hipEventRecord(ev[0], st);
-  if (a.key_index) VRF_LAUNCH_MINW(k_verify_decode_keyed, S, lanes_k_, gk, spread_lds_bytes(gk.x), st, a);
-  else if (a.h_in_tabs) VRF_LAUNCH_MINW(k_verify_decode_skip_h, S, lanes_k_, gk, spread_lds_bytes(gk.x), st, a);
+  if (a.key_index) VRF_LAUNCH_MINW(k_verify_decode_keyed, S, lanes_d, gd, spread_lds_bytes(gd.x), st, a);
+  else if (a.h_in_tabs) VRF_LAUNCH_MINW(k_verify_decode_skip_h, S, lanes_d, gd, spread_lds_bytes(gd.x), st, a);
   else if (a.affine_in) hipLaunchKernelGGL(k_verify_decode_affine<S>, grid_for(a.n), dim3(BLOCK), 0, st, a);
-  else VRF_LAUNCH_MINW(k_verify_decode, S, lanes_k_, gk, spread_lds_bytes(gk.x), st, a);
+  else VRF_LAUNCH_MINW(k_verify_decode, S, lanes_d, gd, spread_lds_bytes(gd.x), st, a);
   if (!ev && !a.key_index && a.n <= STRAUS_FUSE_MAX_ITEMS) {
     dim3 g2 = grid_for(a.n);
     g2.y = 2;

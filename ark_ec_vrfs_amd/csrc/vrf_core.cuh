@@ -123,12 +123,8 @@ VRF_HD DecodeA decode_phase_a(const uint32_t enc[8]) {
   r.den = fe_select(dz, fe_one(), den);
   return r;
 }
-// x from w = num/den; returns validity
-template <class C>
-VRF_HD bool decode_phase_b(Fe<1, 4>& x_out, const DecodeA& a, const FeN& den_inv, const SqrtTables& T) {
-  FeN w = fe_mul(a.num, den_inv);
-  FeN root;
-  bool sq = fe_sqrt_or_zsqrt(root, w, T);
+// the sign of x and the verdict, from a root of num/den (or whatever stands in its place when there is none: sq false)
+VRF_HD bool decode_finish_x(Fe<1, 4>& x_out, const DecodeA& a, const FeN& root, bool sq, const SqrtTables& T) {
   uint32_t xw[8];
   fe_to_u256(xw, root);
   uint32_t nz = 0;
@@ -141,6 +137,24 @@ VRF_HD bool decode_phase_b(Fe<1, 4>& x_out, const DecodeA& a, const FeN& den_inv
   // (SS_SIGN_PARITY) rejects x = 0 with the flag set
   if ((T.str.flags & SS_SIGN_PARITY) && nz == 0 && a.flag) sq = false;
   return a.ok && sq;
+}
+// x from w = num/den; returns validity
+template <class C>
+VRF_HD bool decode_phase_b(Fe<1, 4>& x_out, const DecodeA& a, const FeN& den_inv, const SqrtTables& T) {
+  FeN w = fe_mul(a.num, den_inv);
+  FeN root;
+  bool sq = fe_sqrt_or_zsqrt(root, w, T);
+  return decode_finish_x(x_out, a, root, sq, T);
+}
+// The same x and the same verdict without den^-1: x = num / sqrt(num den), the inverse root out of the square root's own
+// walk (fe_inv_sqrt).  num den is a square exactly when num / den is; num = 0 gives x = 0; den = 0 was replaced by 1 and
+// cleared a.ok in decode_phase_a.  Where there is no root (a rejected point) x is left as num times what the walk made,
+// not the sqrt(Z num / den) of decode_phase_b.
+template <class C>
+VRF_HD bool decode_by_inv_root(Fe<1, 4>& x_out, const DecodeA& a, const SqrtTables& T) {
+  FeN ir;
+  const bool sq = fe_inv_sqrt(ir, fe_mul(a.num, a.den), T);
+  return decode_finish_x(x_out, a, fe_mul(a.num, ir), sq, T);
 }
 
 // Prime-order subgroup membership of a decoded curve point by 2-descent, for curves with full rational
@@ -929,31 +943,33 @@ VRF_HD bool verify_decode_item(const DevTables& T, const uint32_t pk[8], const u
   return valid;
 }
 
-// ---- several proofs per lane: the inversion of decode and of finish is shared by K proofs ----
-// (Montgomery's trick across 3K denominators / 2K Z coordinates; prefix products are parked in the
-// lane's own slice of the HBM workspace, so the loops are rolled and register use stays low.)
+// ---- several proofs per lane: the inversion of finish is shared by K proofs ----
+// (Montgomery's trick across 2K Z coordinates; prefix products are parked in the lane's own slice of the HBM workspace,
+// so the loops are rolled and register use stays low.  The decode stage shares nothing across a lane's proofs: every
+// point is decompressed by its own inverse root, decode_by_inv_root.)
 constexpr int VERIFY_K = 8;                 // max proofs per lane in decode and finish (runtime K <= this)
-constexpr int DEC_SLOT = 4 * NL;            // per point: y | num | den | prefix  (36 words)
+// DEC_SLOT and the scratch_base parameter below are dead; they stay because tests/hostsim_joint and tests/hostsim, which
+// may not change here, size a buffer by the one and pass the other.
+constexpr int DEC_SLOT = 4 * NL;
 
 // points: base pointers of the pk / H / Gamma arrays; items [first, first + K) ∩ [0, n).
-// tabs_base / scratch_base / flags: workspace arrays indexed by item.
+// tabs_base / flags: workspace arrays indexed by item; scratch_base is not touched.
 // NP = 3: pk, H, Gamma (table slots 0, 1, 2); NP = 2 (keyed verification: the key's tables are context
 // resident): H, Gamma (pk is not read, slots 1, 2); NP = 2 with SKIP_H (verification from alpha: H came out of
 // hash-to-curve in this call and its tables are already in slot 1): pk, Gamma (slots 0, 2).
 // JOINT (the GLV suite's IETF verifier): the item's region gets the joint tables instead -- JT_Y from pk, JT_V once H and
 // Gamma of the item are both parked (the loop below meets Gamma first; with SKIP_H, H's affine x, y are already there), from
 // the proof's scalars in c_arr, s_arr.
+// One pass: each point is decoded, decompressed, turned into its tables (or parked) and tested for the subgroup.
 template <class S, int NP = 3, bool SKIP_H = false, bool JOINT = false>
 VRF_HD void verify_decode_multi(int K, const DevTables& T, size_t first, size_t n, const uint8_t* pk,
                                 const uint8_t* hh, const uint8_t* gamma, uint32_t* tabs_base,
                                 uint32_t* scratch_base, uint8_t* flags, uint32_t check_mask = 0,
                                 const uint8_t* c_arr = nullptr, const uint8_t* s_arr = nullptr) {
-  // scratch: K * 108 words owned by this lane = 3K point slots of 36 words
-  uint32_t* scr = scratch_base + first * (3 * DEC_SLOT);
-  FeN run = fe_one();
-  uint64_t bits = 0;                         // per point: bit 2j = sign flag, bit 2j+1 = ok
+  (void)scratch_base;
+  uint32_t valid_mask = 0xffffffffu;
 #pragma unroll 1
-  for (int j = 0; j < NP * K; ++j) {
+  for (int j = NP * K - 1; j >= 0; --j) {
     const size_t item = first + j / NP;
     const int p = SKIP_H ? (j % NP) * 2 : j % NP + (3 - NP);
     if (item < n) {
@@ -962,35 +978,9 @@ VRF_HD void verify_decode_multi(int K, const DevTables& T, size_t first, size_t 
       const uint32_t* w = reinterpret_cast<const uint32_t*>(src + item * 32);
 #pragma unroll
       for (int k = 0; k < 8; ++k) enc[k] = w[k];
-      DecodeA a = decode_phase_a<S>(enc);
-      uint32_t* slot = scr + j * DEC_SLOT;
-      fe_store(slot, a.y);
-      fe_store(slot + NL, a.num);
-      fe_store(slot + 2 * NL, a.den);
-      fe_store(slot + 3 * NL, run);
-      run = fe_mul(run, a.den);
-      bits |= (uint64_t)((a.flag ? 1u : 0u) | (a.ok ? 2u : 0u)) << (2 * j);
-    }
-  }
-  FeN inv = fe_inv(run);
-  uint32_t valid_mask = 0xffffffffu;
-#pragma unroll 1
-  for (int j = NP * K - 1; j >= 0; --j) {
-    const size_t item = first + j / NP;
-    const int p = SKIP_H ? (j % NP) * 2 : j % NP + (3 - NP);
-    if (item < n) {
-      const uint32_t* slot = scr + j * DEC_SLOT;
-      DecodeA a;
-      a.y = fe_load<1, 2>(slot);
-      a.num = fe_load<1, 6>(slot + NL);
-      a.den = fe_load<1, 2>(slot + 2 * NL);
-      FeN prefix = fe_load<1, 2>(slot + 3 * NL);
-      a.flag = (bits >> (2 * j)) & 1;
-      a.ok = (bits >> (2 * j + 1)) & 1;
-      FeN di = fe_mul(inv, prefix);
-      inv = fe_mul(inv, a.den);
+      const DecodeA a = decode_phase_a<S>(enc);
       Fe<1, 4> x;
-      bool ok = decode_phase_b<S>(x, a, di, T.sq);
+      bool ok = decode_by_inv_root<S>(x, a, T.sq);
       if constexpr (JOINT) {
         uint32_t* reg = tabs_base + item * (VERIFY_TABS * WIN_TABLE_WORDS);
         if (p == 0) build_joint_y_table<S>(reg, x, a.y);

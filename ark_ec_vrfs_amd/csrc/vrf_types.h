@@ -6,7 +6,9 @@
 #include <cstddef>
 #include <cstdint>
 
+#ifndef VRF_HD      // a host test build may define it without the forced inlining (the sanitizer build of tests/hostsim_pace)
 #define VRF_HD __host__ __device__ __forceinline__
+#endif
 
 namespace vrf {
 
@@ -76,7 +78,8 @@ struct Workspace {
 
 struct VerifyArgs {
   int suite;
-  int k_lane;
+  int k_lane;                              // proofs per lane in the finish launch (they share its inversion)
+  int k_decode;                            // proofs per lane in the decode launches; 0: k_lane
   size_t n;
   const uint8_t *pk, *h, *gamma, *c, *s;   // affine_in != 0: pk, h, gamma are 64-byte x || y
   int affine_in;
