@@ -49,7 +49,8 @@ SYMBOLS = [
     "vrfhip_ietf_verify_batch_multi", "vrfhip_ietf_prove_batch_multi",
     "vrfhip_pedersen_prove_batch_multi", "vrfhip_pedersen_verify_batch_multi",
     "vrfhip_ietf_verify_batch_affine_multi", "vrfhip_pedersen_verify_batch_affine_multi",
-    "vrfhip_test_point_add", "vrfhip_test_scalar_mul", "vrfhip_test_verify_uv", "vrfhip_test_sha512", "vrfhip_test_xmd", "vrfhip_test_batch_digest",
+    "vrfhip_test_point_add", "vrfhip_test_scalar_mul", "vrfhip_test_verify_uv", "vrfhip_test_pedersen_verify_c",
+    "vrfhip_test_sha512", "vrfhip_test_xmd", "vrfhip_test_batch_digest",
 ]
 
 
@@ -83,7 +84,7 @@ def source_stamp() -> str:
     return h.hexdigest()
 
 
-ABI_VERSION = 145      # vrfhip_abi_version() of the library this binding was written against
+ABI_VERSION = 146      # vrfhip_abi_version() of the library this binding was written against
 
 
 def load() -> ctypes.CDLL:
@@ -218,6 +219,7 @@ def load() -> ctypes.CDLL:
     lib.vrfhip_test_point_add.argtypes = [c_void_p, c_size_t, P, P, P, P]
     lib.vrfhip_test_scalar_mul.argtypes = [c_void_p, c_size_t, P, P, P, P]
     lib.vrfhip_test_verify_uv.argtypes = [c_void_p, c_size_t, ctypes.c_int32, P, c_void_p, P, P, P, P, P, P, P, P]
+    lib.vrfhip_test_pedersen_verify_c.argtypes = [c_void_p, c_size_t, ctypes.c_int32, P, P, P, P, P, P, P, P, P]
     lib.vrfhip_test_sha512.argtypes = [c_void_p, c_size_t, P, P, c_uint32, P]
     lib.vrfhip_test_xmd.argtypes = [c_void_p, c_size_t, P, P, c_uint32, P]
     lib.vrfhip_test_batch_digest.argtypes = [c_void_p, c_size_t, c_int32, P, P, P, P, c_uint32, ctypes.c_uint64, P]

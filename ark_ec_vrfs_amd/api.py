@@ -954,6 +954,20 @@ class Context:
             _ptr(out), _ptr(c), _ptr(s), _ptr(u), _ptr(v), _ptr(st)), "vrfhip_test_verify_uv")
         return u, v, st
 
+    def test_pedersen_verify_c(self, inp, out, pk_com, r, ok, c, s, sb, affine=False):
+        """Per-proof Pedersen verification with the challenge c supplied instead of hashed (vrfhip_test_pedersen_verify_c):
+        the launches of pedersen_verify_batch (affine: of its x || y form) for this batch size; status per item."""
+        pw = 64 if affine else self.point_bytes()
+        pts = [np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, pw) for x in (inp, out, pk_com, r, ok)]
+        scs = [np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 32) for x in (c, s, sb)]
+        n = pts[0].shape[0]
+        if not all(x.shape[0] == n for x in pts + scs):
+            raise ValueError("ragged batch")
+        st = np.empty(n, np.uint8)
+        _lib.check(self._lib.vrfhip_test_pedersen_verify_c(self._h, n, 1 if affine else 0, *(_ptr(x) for x in pts + scs), _ptr(st)),
+                   "vrfhip_test_pedersen_verify_c")
+        return st
+
     def _test_hash(self, fn, name, msgs, width):
         blob, off = _pack_var([bytes(m) for m in msgs])
         out = np.empty((len(msgs), width), np.uint8)

@@ -409,7 +409,7 @@ int32_t stage_blob(vrfhip_ctx* ctx, const StagedBlob& b, Blob* out) {
 
 extern "C" {
 
-int32_t vrfhip_abi_version(void) { return 145; }
+int32_t vrfhip_abi_version(void) { return 146; }
 
 const char* vrfhip_last_error(void) { return g_last_error.c_str(); }
 
@@ -1388,8 +1388,9 @@ struct PedStage {
 };
 
 // affine: the five point arrays are 64-byte x || y (canonical, or Montgomery-256 under VRFHIP_FLAG_COORDS_MONT256)
+// d_c (vrfhip_test_pedersen_verify_c; n x 32 B): the launchers put it over the challenge their decode stage hashed
 int32_t ped_verify_dev_impl(vrfhip_ctx* ctx, size_t n, bool affine, const PedIn& in, const Blob& ad, uint8_t* d_status,
-                            void* stream) {
+                            void* stream, const uint8_t* d_c = nullptr) {
   if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
   if (n == 0) return VRFHIP_SUCCESS;
   if (in.any_null() || !d_status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
@@ -1408,6 +1409,7 @@ int32_t ped_verify_dev_impl(vrfhip_ctx* ctx, size_t n, bool affine, const PedIn&
       a.affine_in = ctx->affine_in(affine);
       a.ad = ad.view(base);
       a.status = d_status + base;
+      if (d_c) a.c_in = d_c + base * 32;
     };
     if (ctx->sw) {
       p256::PedVerifyArgs a{};
@@ -2867,6 +2869,36 @@ int32_t vrfhip_test_verify_uv(vrfhip_ctx* ctx, size_t n, int32_t affine, const u
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(u_out, d_u, n * ow, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipMemcpyAsync(v_out, d_v, n * ow, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+
+// Pedersen verification with the challenge supplied: ped_verify_dev_impl with d_c set, so the decode, ladder and finish
+// launches and their shape are the ones vrfhip_pedersen_verify_batch[_affine] gets for this n; the hashed challenge is
+// overwritten between the decode and the ladder launches.
+int32_t vrfhip_test_pedersen_verify_c(vrfhip_ctx* ctx, size_t n, int32_t affine, const uint8_t* input, const uint8_t* output,
+                                      const uint8_t* pk_com, const uint8_t* r, const uint8_t* ok, const uint8_t* c,
+                                      const uint8_t* s, const uint8_t* sb, uint8_t* status) {
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (n == 0) return VRFHIP_SUCCESS;
+  const PedIn in{input, output, pk_com, r, ok, s, sb};
+  if (in.any_null() || !c || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  const size_t pw = affine ? 64 : ctx->pt_bytes();
+  PedStage d;
+  uint8_t *d_c, *d_st;
+  int32_t rc = stage_layout(ctx, [&](Stage& sg) {
+    d.take(sg, n, pw);
+    d_c = sg.take(n * 32);
+    d_st = sg.take(n);
+  });
+  if (rc) return rc;
+  if ((rc = d.send(ctx, in, n, pw))) return rc;
+  HIP_TRY(hipMemcpyAsync(d_c, c, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  rc = ped_verify_dev_impl(ctx, n, affine != 0, d.dev(), Blob{nullptr, nullptr, 0, true}, d_st, ctx->stream, d_c);
+  if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return VRFHIP_SUCCESS;

@@ -59,6 +59,17 @@ VRF_HD void fr_reduce256(uint32_t out[8], const uint32_t x[8]) {
   fr_montmul<C>(out, x, r1);                 // x * (2^256 mod r) / 2^256 = x mod r
 }
 
+// w < 2^(8 nbytes), nbytes in 1..32: a supplied challenge fits `Suite::CHALLENGE_LEN` bytes (vrfhip_test_pedersen_verify_c)
+VRF_HD bool u256_fits_bytes(const uint32_t w[8], uint32_t nbytes) {
+  uint32_t over = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const uint32_t have = nbytes > 4u * j ? nbytes - 4u * j : 0u;      // bytes of word j below the bound
+    over |= have >= 4u ? 0u : have == 0u ? w[j] : (w[j] >> (8u * have));
+  }
+  return over == 0;
+}
+
 template <class C>
 VRF_HD void fr_add(uint32_t out[8], const uint32_t a[8], const uint32_t b[8]) {   // a, b < r
   uint32_t s[8], d[8];

@@ -474,6 +474,19 @@ __global__ void __launch_bounds__(BLOCK, 2) k_bsw_ped_verify_decode_affine(Peder
   bsw_ped_verify_decode<true>(a, i);
 }
 
+// vrfhip_test_pedersen_verify_c (a.c_in): the supplied challenge over the hashed one, as k_ped_verify_set_c (k_pedersen.hip)
+__global__ void __launch_bounds__(BLOCK) k_bsw_ped_verify_set_c(PedersenVerifyArgs a) {
+  size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  uint32_t cw[8], c[8];
+  load32(cw, a.c_in, i);
+  const bool fits = challenge_supplied<BswS>(c, cw, a.T.sq.str);
+  uint32_t* aux = a.ws.aux + i * AUX_WORDS;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) aux[j] = c[j];
+  if (!fits) a.ws.flags[i] = 0;
+}
+
 // HALF 0: s*H - c*Gamma ; HALF 1: s*G - c*pk_com + sb*B
 template <int HALF>
 __global__ void __launch_bounds__(BLOCK) k_bsw_ped_verify_straus(PedersenVerifyArgs a) {
@@ -672,6 +685,7 @@ void launch_bsw_pedersen_verify(const PedersenVerifyArgs& a, hipStream_t st, hip
   if (ev) (void)hipEventRecord(ev[0], st);
   if (a.affine_in) hipLaunchKernelGGL(k_bsw_ped_verify_decode_affine, grid_for(a.n), dim3(BLOCK), 0, st, a);
   else hipLaunchKernelGGL(k_bsw_ped_verify_decode, grid_for(a.n), dim3(BLOCK), 0, st, a);
+  if (a.c_in) hipLaunchKernelGGL(k_bsw_ped_verify_set_c, grid_for(a.n), dim3(BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[1], st);
   hipLaunchKernelGGL(k_bsw_ped_verify_straus<0>, grid_for(a.n), dim3(BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[2], st);

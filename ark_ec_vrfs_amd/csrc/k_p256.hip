@@ -452,6 +452,16 @@ __global__ void __launch_bounds__(P256_BLOCK) k_p256_ped_verify_decode_affine(p2
   ws_store8(a.ws.sc, cap, i, 16, sb);
   a.ws.flags[i] = ok ? 1 : 0;
 }
+// vrfhip_test_pedersen_verify_c (a.c_in): the supplied challenge over the one the decode stage hashed (slot 0 of ws.sc); one
+// that does not fit the challenge length clears the item's flag: the ladders skip it, the finish stage reports 2
+__global__ void __launch_bounds__(P256_BLOCK) k_p256_ped_verify_set_c(p256::PedVerifyArgs a) {
+  const size_t i = (size_t)blockIdx.x * P256_BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  uint32_t c[8];
+  const bool fits = p256_challenge_supplied(c, a.c_in + i * 32, a.str.challenge_len);
+  ws_store8(a.ws.sc, a.ws.cap, i, 0, c);
+  if (!fits) a.ws.flags[i] = 0;
+}
 // WHICH = 0: s H - c Gamma - Ok = O (two tables); 1: s G + sb B - c pk_com - R = O (two comb walks, one table).  The
 // verdict of each equation goes to word WHICH of the item's result record.
 template <int WHICH>
@@ -607,6 +617,7 @@ void launch_pedersen_verify(const PedVerifyArgs& a, hipStream_t st, hipEvent_t* 
   if (ev) (void)hipEventRecord(ev[0], st);
   if (a.affine_in) hipLaunchKernelGGL(k_p256_ped_verify_decode_affine, dim3(g), dim3(P256_BLOCK), 0, st, a);
   else hipLaunchKernelGGL(k_p256_ped_verify_decode, dim3(g), dim3(P256_BLOCK), 0, st, a);
+  if (a.c_in) hipLaunchKernelGGL(k_p256_ped_verify_set_c, dim3(g), dim3(P256_BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[1], st);
   hipLaunchKernelGGL(k_p256_ped_verify_mul<0>, dim3(g), dim3(P256_BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[2], st);

@@ -43,6 +43,21 @@ __global__ void __launch_bounds__(BLOCK, MINW) k_ped_verify_decode_affine(Peders
   a.ws.flags[i] = ok ? 1 : 0;
 }
 
+// vrfhip_test_pedersen_verify_c (a.c_in): the supplied challenge over the one the decode stage hashed; one that does not fit
+// the suite's challenge length takes the item's flag with it (InvalidData from the finish stage)
+template <class S>
+__global__ void __launch_bounds__(BLOCK) k_ped_verify_set_c(PedersenVerifyArgs a) {
+  size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a.n) return;
+  uint32_t cw[8], c[8];
+  load32(cw, a.c_in, i);
+  const bool fits = challenge_supplied<S>(c, cw, a.T.sq.str);
+  uint32_t* aux = a.ws.aux + i * AUX_WORDS;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) aux[j] = c[j];
+  if (!fits) a.ws.flags[i] = 0;
+}
+
 // HALF 0: s*H - c*Gamma ; HALF 1: s*G - c*pk_com + sb*B.  Separate launches keep each wave uniform.
 template <class S, int HALF>
 __global__ void __launch_bounds__(BLOCK) k_ped_verify_straus(PedersenVerifyArgs a) {
@@ -94,6 +109,7 @@ static void launch_ped_t(const PedersenVerifyArgs& a, hipStream_t st, hipEvent_t
   if (ev) (void)hipEventRecord(ev[0], st);
   if (a.affine_in) VRF_LAUNCH_MINW(k_ped_verify_decode_affine, S, a.n, grid_for(a.n), 0, st, a);
   else VRF_LAUNCH_MINW(k_ped_verify_decode, S, a.n, grid_for(a.n), 0, st, a);
+  if (a.c_in) hipLaunchKernelGGL(k_ped_verify_set_c<S>, grid_for(a.n), dim3(BLOCK), 0, st, a);
   if (ev) (void)hipEventRecord(ev[1], st);
   if (!ev && a.n <= STRAUS_FUSE_MAX_ITEMS) {
     dim3 g2 = grid_for(a.n);

@@ -89,6 +89,9 @@ struct PedVerifyArgs {
   Ws ws;
   const uint32_t *comb, *comb_b;
   SuiteStr str;
+  // vrfhip_test_pedersen_verify_c (c_in != nullptr; n x 32 B, big-endian): after the decode launch k_p256_ped_verify_set_c
+  // replaces the hashed challenge (slot 0 of ws.sc) by c_in[i]; c_in[i] >= 2^(8 challenge_len) clears the item's flag
+  const uint8_t* c_in;
 };
 
 // ---- multi-scalar multiplication and the batched Pedersen verifier (k_p256_msm.hip) ----

@@ -657,6 +657,12 @@ VRF_HD bool p256_ped_verify_decode_affine_item(FeN (&x)[5], FeN (&y)[5], uint32_
   const bool s_ok = p256_scalar_decode(s, s_be), sb_ok = p256_scalar_decode(sb, sb_be);
   return ok && s_ok && sb_ok;
 }
+// vrfhip_test_pedersen_verify_c: a supplied challenge (32 bytes big-endian) as the words p256_challenge leaves its own in;
+// false: it does not fit challenge_len bytes
+VRF_HD bool p256_challenge_supplied(uint32_t c[8], const uint8_t* cb, uint32_t challenge_len) {
+  load_be256(c, cb);
+  return u256_fits_bytes(c, challenge_len);
+}
 // verify, stage 2: the two equations as "is the point at infinity":  s H - c Gamma - Ok  and  s G + sb B - c pk_com - R
 VRF_HD bool sw_is_infinity(const PtW& p) { return fe_is_zero(p.Z); }
 VRF_HD bool p256_ped_verify_eq_h(const uint32_t* tabH, const uint32_t* tabG, size_t stride, const FeN& okx, const FeN& oky,

@@ -766,6 +766,18 @@ VRF_HD void proof_challenge_decode(uint32_t out[8], const uint32_t c[8], const S
   }
 }
 
+// vrfhip_test_pedersen_verify_c: a challenge supplied in place of the hashed one, brought to the form challenge5 leaves its
+// own in (below 2^(8 challenge_len), reduced mod r).  false: it does not fit challenge_len bytes, out is zero.
+template <class S>
+VRF_HD bool challenge_supplied(uint32_t out[8], const uint32_t c[8], const SuiteStr& ss) {
+  const bool fits = u256_fits_bytes(c, ss.challenge_len);
+  uint32_t cr[8];
+  fr_reduce256<S>(cr, c);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) out[j] = fits ? cr[j] : 0u;
+  return fits;
+}
+
 // ------------------------------------------------------------------------ IETF verify
 // [ref src/lib.rs:14 `ietf::Verifier::verify`]  U = s*G - c*Y, V = s*H - c*Gamma, accept iff
 // challenge(Y, H, Gamma, U, V, ad) == c.  Three stages (three kernels):

@@ -129,6 +129,10 @@ struct PedersenVerifyArgs {
   uint8_t* status;
   Workspace ws;
   DevTables T;
+  // vrfhip_test_pedersen_verify_c (c_in != nullptr; n x 32 B, little-endian): between the decode launch and the ladder launches
+  // one more kernel replaces the challenge the decode stage hashed (ws.aux[i][0..8]) by c_in[i]; an item whose c_in is
+  // 2^(8 challenge_len) or more loses its flag (status 2).  nullptr: the launch sequence of every other caller.
+  const uint8_t* c_in;
 };
 
 // Device-side layout of one MSM over n points (all regions inside one workspace allocation; msm.cuh).

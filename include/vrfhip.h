@@ -813,6 +813,19 @@ int32_t vrfhip_test_scalar_mul(vrfhip_ctx* ctx, size_t n, const uint8_t* scalars
 int32_t vrfhip_test_verify_uv(vrfhip_ctx* ctx, size_t n, int32_t affine, const uint8_t* pk, const vrfhip_keyset* keys,
                               const uint32_t* key_index, const uint8_t* input, const uint8_t* output, const uint8_t* c,
                               const uint8_t* s, uint8_t* u_out, uint8_t* v_out, uint8_t* status);
+/* Test-only: per-proof Pedersen verification with the challenge SUPPLIED instead of hashed.
+ *   accept iff  s*input - c*output == ok  and  s*G + sb*B - c*pk_com == r   (`pedersen::Verifier::verify`, src/lib.rs:14)
+ * The real c is a hash of the five points, so no caller can build an accepting item at a chosen (c, s, sb); with c given,
+ * ok and r can be computed for any of them, and the verdict then says whether the ladders and the finish stage are right.
+ * The call runs the decode, ladder and finish launches that vrfhip_pedersen_verify_batch (affine != 0: _affine, the five
+ * point arrays as n x 64 bytes x || y, VRFHIP_FLAG_COORDS_MONT256 as there) chooses for this n; between the decode and the
+ * ladder launches one small kernel overwrites the challenge the decode stage stored.  c: n x 32 bytes in the byte order
+ * of the suite's scalars (little-endian; big-endian on secp256r1); taken mod r where challenge_len = 32.
+ * status[i]: 2 where a point does not decode (subgroup tests as the context's flags say), s or sb >= r, or
+ * c >= 2^(8 * challenge_len); else 1 where an equation fails; else 0.  All arrays are host memory. */
+int32_t vrfhip_test_pedersen_verify_c(vrfhip_ctx* ctx, size_t n, int32_t affine, const uint8_t* input, const uint8_t* output,
+                                      const uint8_t* pk_com, const uint8_t* r, const uint8_t* ok, const uint8_t* c,
+                                      const uint8_t* s, const uint8_t* sb, uint8_t* status);
 int32_t vrfhip_test_sha512(vrfhip_ctx* ctx, size_t n, const uint8_t* msg, const uint32_t* msg_off, uint32_t msg_len,
                            uint8_t* out);
 int32_t vrfhip_test_xmd(vrfhip_ctx* ctx, size_t n, const uint8_t* msg, const uint32_t* msg_off, uint32_t msg_len,

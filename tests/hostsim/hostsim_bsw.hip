@@ -22,6 +22,7 @@ SqrtTables tables() {
 FeN in(const uint8_t* b) { uint32_t w[8]; memcpy(w, b, 32); return fe_from_u256(w); }
 template <int L, int V> void out(uint8_t* b, const Fe<L, V>& a) { uint32_t w[8]; fe_to_u256(w, a); memcpy(b, w, 32); }
 }
+#include "pedersen_c.inc"
 extern "C" {
 // bit 0: decodes; bit 1: the point at infinity; bit 2: in the prime-order subgroup.  te_xy / sw_xy: x || y little-endian
 int hb_decode(const uint8_t* enc, uint8_t* te_xy, uint8_t* sw_xy) {
@@ -105,6 +106,49 @@ int hb_verify_uv(uint32_t challenge_len, uint32_t check_mask, const uint8_t* pk,
   store33(u, 0, bsw_encode_frac(f[0], di[0]), valid);
   store33(v, 0, bsw_encode_frac(f[1], di[1]), valid);
   return valid ? 0 : 2;
+}
+// Per-proof Pedersen verification with the challenge supplied (vrfhip_test_pedersen_verify_c) as k_bsw.hip stages it:
+// bsw_ped_verify_decode's shared-inversion way in (chain order pk_com, H, Gamma, R, Ok; subgroup tests of check_mask), then
+// the Edwards suite's override, ladders and finish (pedersen_c.inc).  0, 1 or 2.
+int hb_pedersen_verify_c(uint32_t challenge_len, uint32_t check_mask, const uint8_t* h, const uint8_t* g, const uint8_t* pk_com,
+                         const uint8_t* r, const uint8_t* ok, const uint8_t* c, const uint8_t* s, const uint8_t* sb) {
+  static std::vector<uint32_t> combs[2];                   // generator, blinding base: by the device's own builder
+  if (combs[0].empty()) {
+    std::vector<uint32_t> prefix((size_t)GC_SEG * NL);
+    for (int which = 0; which < 2; ++which) {
+      combs[which].assign(GCOMB_WORDS, 0);
+      for (int w = 0; w < GC_ROWS; ++w)
+        for (int seg = 0; seg < GC_SEGS; ++seg)
+          gcomb_build_segment<BswS>(combs[which].data(), prefix.data(), which ? BswS::bx() : BswS::gx(), which ? BswS::by() : BswS::gy(), w, seg);
+    }
+  }
+  DevTables T{};
+  T.sq = tables();
+  T.sq.str.challenge_len = challenge_len;
+  T.g_comb = combs[0].data(); T.b_comb = combs[1].data();
+  const uint8_t* src[5] = {pk_com, h, g, r, ok};           // chain order
+  const uint32_t chk[5] = {CHK_PROOF, CHK_INPUT, CHK_OUTPUT, CHK_PROOF, CHK_PROOF};
+  std::vector<uint32_t> tabs(VERIFY_TABS * WIN_TABLE_WORDS), pts(PROVE_PTS_WORDS);
+  uint32_t scr[5 * BSW_SLOT], st[5];
+  FeN run = fe_one();
+  for (int k = 0; k < 5; ++k) st[k] = bsw_in_a(scr + k * BSW_SLOT, run, load33(src[k], 0), T.sq);
+  FeN inv = fe_inv(run);
+  bool valid = true;
+  for (int k = 4; k >= 0; --k) {
+    const int p = k == 0 ? 2 : k == 1 ? 0 : k == 2 ? 1 : k;             // slot: H, Gamma, pk_com, R, Ok
+    FeN x, y;
+    bsw_in_b(x, y, inv, scr + k * BSW_SLOT, (st[k] & BSW_A_INF) != 0);
+    valid = valid && (st[k] & BSW_A_OK) != 0;
+    if (check_mask & chk[k]) valid = in_prime_subgroup<BswS>(x, y, T.sq) && valid;
+    if (p < 3) {
+      build_glv_tables<BswS>(tabs.data() + p * 2 * WIN_TABLE_WORDS, x, y);
+    } else {
+      uint32_t* dst = pts.data() + (p == 3 ? PED_R_OFF : PED_OK_OFF);
+      fe_store(dst, x);
+      fe_store(dst + NL, y);
+    }
+  }
+  return (int)host_pedersen_ladders_c<BswS>(T, valid, tabs.data(), pts.data(), c, s, sb);
 }
 void hb_canonical(const uint8_t* enc, uint8_t* o) { store33(o, 0, enc33_canonical(load33(enc, 0))); }
 void hb_challenge(const uint8_t* pts, const uint8_t* ad, uint32_t ad_len, uint8_t* c) {

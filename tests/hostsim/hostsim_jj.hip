@@ -34,6 +34,7 @@ struct HostTablesJ {
 HostTablesJ& HJ() { static HostTablesJ h; h.t.sq.str = g_hj_str; return h; }
 }
 #include "verify_uv.inc"
+#include "pedersen_c.inc"
 static uint32_t g_check_mask_jj = 0;   // CHK_* bits for the decode stages (0 = on-curve only)
 extern "C" {
 void hj_set_check_mask(uint32_t m) { g_check_mask_jj = m; }
@@ -120,5 +121,9 @@ uint32_t hj_pedersen_verify(const uint8_t* h, const uint8_t* g, const uint8_t* p
   pedersen_verify_straus_item<SJ, 0>(pts.data(), HJ().t, tabs.data(), c, s2, sb2);
   pedersen_verify_straus_item<SJ, 1>(pts.data() + UV_WORDS, HJ().t, tabs.data(), c, s2, sb2);
   return pedersen_verify_finish_item<SJ>(pts.data(), s, sb, valid);
+}
+uint32_t hj_pedersen_verify_c(uint32_t challenge_len, const uint8_t* h, const uint8_t* g, const uint8_t* pk_com, const uint8_t* r,
+                              const uint8_t* ok, const uint8_t* c, const uint8_t* s, const uint8_t* sb) {
+  return host_pedersen_verify_c<SJ>(HJ().t, challenge_len, g_check_mask_jj, h, g, pk_com, r, ok, c, s, sb);
 }
 }

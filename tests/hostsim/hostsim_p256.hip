@@ -199,4 +199,23 @@ int hp_ped_verify(const uint8_t* h, const uint8_t* gamma, const uint8_t* pk_com,
   const bool e2 = p256_ped_verify_eq_g(comb().data(), g_comb_b.data(), tp.data(), 1, x[3], y[3], s, sb, c, cw);
   return (e1 && e2) ? 0 : 1;
 }
+// the same verification with the challenge supplied (vrfhip_test_pedersen_verify_c): k_p256_ped_verify_set_c's override
+// between the decode and the two equations; challenge_len replaces the suite string's for this call
+int hp_ped_verify_c(uint32_t challenge_len, const uint8_t* h, const uint8_t* gamma, const uint8_t* pk_com, const uint8_t* r,
+                    const uint8_t* ok, const uint8_t* c_be, const uint8_t* s_be, const uint8_t* sb_be) {
+  SuiteStr str = g_str;
+  str.challenge_len = challenge_len;
+  FeN x[5], y[5]; uint32_t c[8], s[8], sb[8];
+  bool valid = p256_ped_verify_decode_item(x, y, c, s, sb, h, gamma, pk_com, r, ok, s_be, sb_be, nullptr, 0, str);
+  valid = p256_challenge_supplied(c, c_be, challenge_len) && valid;
+  if (!valid) return 2;
+  std::vector<uint32_t> th(SW_TABLE_WORDS), tg(SW_TABLE_WORDS), tp(SW_TABLE_WORDS);
+  sw_build_table(th.data(), 1, sw_from_affine(x[0], y[0]));
+  sw_build_table(tg.data(), 1, sw_from_affine(x[1], y[1]));
+  sw_build_table(tp.data(), 1, sw_from_affine(x[2], y[2]));
+  const int cw = sw_challenge_windows(str);
+  const bool e1 = p256_ped_verify_eq_h(th.data(), tg.data(), 1, x[4], y[4], s, c, cw);
+  const bool e2 = p256_ped_verify_eq_g(comb().data(), g_comb_b.data(), tp.data(), 1, x[3], y[3], s, sb, c, cw);
+  return (e1 && e2) ? 0 : 1;
+}
 }

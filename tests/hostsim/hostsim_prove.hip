@@ -36,6 +36,7 @@ struct HostTables {
 };
 HostTables& HT() { static HostTables h; h.t.sq.str = g_hs_str; return h; }      // strings may change between calls
 }
+#include "pedersen_c.inc"
 static uint32_t g_check_mask_p = 0;    // CHK_* bits for the decode stages (0 = on-curve only)
 extern "C" {
 void hs_set_check_mask_prove(uint32_t m) { g_check_mask_p = m; }
@@ -107,6 +108,11 @@ uint32_t hs_pedersen_verify(const uint8_t* h, const uint8_t* g, const uint8_t* p
   pedersen_verify_straus_item<SuiteBS, 0>(pts.data(), HT().t, tabs.data(), c, s2, sb2);
   pedersen_verify_straus_item<SuiteBS, 1>(pts.data() + UV_WORDS, HT().t, tabs.data(), c, s2, sb2);
   return pedersen_verify_finish_item<SuiteBS>(pts.data(), s, sb, valid);
+}
+// the same verification with the challenge supplied (pedersen_c.inc), Bandersnatch
+uint32_t hs_pedersen_verify_c(uint32_t challenge_len, const uint8_t* h, const uint8_t* g, const uint8_t* pk_com, const uint8_t* r,
+                              const uint8_t* ok, const uint8_t* c, const uint8_t* s, const uint8_t* sb) {
+  return host_pedersen_verify_c<SuiteBS>(HT().t, challenge_len, g_check_mask_p, h, g, pk_com, r, ok, c, s, sb);
 }
 // batch prove through the K-per-lane prepare, exactly as the kernels run it; out: n x (gamma | c | s | pk | h)
 void hs_ietf_prove_multi(uint32_t n, const uint8_t* sk, const uint8_t* msgs, uint32_t msg_len, const uint8_t* ad,

@@ -50,6 +50,7 @@ static FeN in(const uint8_t* b) { uint32_t w[8]; memcpy(w, b, 32); return fe_fro
 template <int L, int V> static void out(uint8_t* b, const Fe<L, V>& a) { uint32_t w[8]; fe_to_u256(w, a); memcpy(b, w, 32); }
 }
 #include "verify_uv.inc"
+#include "pedersen_c.inc"
 static uint32_t g_check_mask_x = 0;   // CHK_* bits for the decode stages (0 = on-curve only)
 extern "C" {
 void hx_set_check_mask(uint32_t m) { g_check_mask_x = m; }
@@ -217,5 +218,10 @@ uint32_t hx_pedersen_verify(const uint8_t* h, const uint8_t* g, const uint8_t* p
   pedersen_verify_straus_item<SX, 0>(pts.data(), HX().t, tabs.data(), c, s2, sb2);
   pedersen_verify_straus_item<SX, 1>(pts.data() + UV_WORDS, HX().t, tabs.data(), c, s2, sb2);
   return pedersen_verify_finish_item<SX>(pts.data(), s, sb, valid);
+}
+// the same verification with the challenge supplied (pedersen_c.inc)
+uint32_t hx_pedersen_verify_c(uint32_t challenge_len, const uint8_t* h, const uint8_t* g, const uint8_t* pk_com, const uint8_t* r,
+                              const uint8_t* ok, const uint8_t* c, const uint8_t* s, const uint8_t* sb) {
+  return host_pedersen_verify_c<SX>(HX().t, challenge_len, g_check_mask_x, h, g, pk_com, r, ok, c, s, sb);
 }
 }
