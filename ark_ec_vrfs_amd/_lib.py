@@ -37,6 +37,9 @@ SYMBOLS = [
     "vrfhip_g1_decode_batch", "vrfhip_g1_decode_batch_dev", "vrfhip_g1_validate_batch", "vrfhip_g1_validate_batch_dev",
     "vrfhip_g1_encode_batch", "vrfhip_g1_encode_batch_dev", "vrfhip_g1_lincomb_batch", "vrfhip_g1_lincomb_batch_dev",
     "vrfhip_kzg_check_batch", "vrfhip_kzg_check_batch_dev", "vrfhip_kzg_check_batch_rlc", "vrfhip_kzg_check_batch_rlc_dev",
+    "vrfhip_g1_srs_create", "vrfhip_g1_srs_destroy", "vrfhip_g1_srs_size", "vrfhip_g1_srs_bytes",
+    "vrfhip_kzg_commit_batch", "vrfhip_kzg_commit_batch_dev", "vrfhip_kzg_open_batch", "vrfhip_kzg_open_batch_dev",
+    "vrfhip_test_g1_msm_groups",
     "vrfhip_kzg_multi_check_batch", "vrfhip_kzg_multi_check_batch_dev", "vrfhip_kzg_multi_check_batch_rlc",
     "vrfhip_kzg_multi_check_batch_rlc_dev",
     "vrfhip_hash_to_curve_batch", "vrfhip_hash_to_curve_batch_dev",
@@ -186,6 +189,16 @@ def load() -> ctypes.CDLL:
     lib.vrfhip_kzg_check_batch_dev.argtypes = [c_void_p, c_size_t, P, P, P, P, P, P, c_void_p]
     lib.vrfhip_kzg_check_batch_rlc.argtypes = [c_void_p, c_size_t, P, P, P, P, P, P, P, POINTER(c_int32)]
     lib.vrfhip_kzg_check_batch_rlc_dev.argtypes = [c_void_p, c_size_t, P, P, P, P, P, P, P, P, P, c_void_p]
+    lib.vrfhip_g1_srs_create.argtypes = [c_void_p, c_size_t, P, P, POINTER(c_void_p)]
+    lib.vrfhip_g1_srs_destroy.argtypes = [c_void_p]
+    lib.vrfhip_g1_srs_destroy.restype = None
+    lib.vrfhip_g1_srs_size.argtypes = lib.vrfhip_g1_srs_bytes.argtypes = [c_void_p]
+    lib.vrfhip_g1_srs_size.restype = lib.vrfhip_g1_srs_bytes.restype = c_size_t
+    lib.vrfhip_kzg_commit_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, P, P, P, P]
+    lib.vrfhip_kzg_commit_batch_dev.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, P, P, P, P, c_void_p]
+    lib.vrfhip_kzg_open_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, P, P, P, P, P, P]
+    lib.vrfhip_kzg_open_batch_dev.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, P, P, P, P, P, P, c_void_p]
+    lib.vrfhip_test_g1_msm_groups.argtypes = [c_void_p, c_size_t, c_int32, c_int32]
     kzgm = [c_void_p, c_size_t, c_uint32, c_uint32, c_uint32] + [P] * 8    # ctx, n, (k, m, p), the seven arrays, vk
     lib.vrfhip_kzg_multi_check_batch.argtypes = kzgm + [P]
     lib.vrfhip_kzg_multi_check_batch_dev.argtypes = kzgm + [P, c_void_p]
@@ -226,7 +239,8 @@ def load() -> ctypes.CDLL:
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("vrfhip_last_error", "vrfhip_ctx_destroy", "vrfhip_ctx_workspace_bytes", "vrfhip_host_free",
-                        "vrfhip_keyset_destroy", "vrfhip_keyset_bytes", "vrfhip_ctx_get_flags", "vrfhip_ctx_point_bytes",
+                        "vrfhip_keyset_destroy", "vrfhip_keyset_bytes", "vrfhip_g1_srs_destroy", "vrfhip_g1_srs_size",
+                        "vrfhip_g1_srs_bytes", "vrfhip_ctx_get_flags", "vrfhip_ctx_point_bytes",
                         "vrfhip_ctx_hash_bytes"):
             fn.restype = c_int32
     _lib = lib

@@ -776,6 +776,67 @@ class Context:
                                                             None if sums is None else sums.data_ptr(), st),
                    "vrfhip_kzg_check_batch_rlc_dev")
 
+    # ---- KZG commitments and openings over a resident base set -------------------------------
+    def g1_srs_create(self, points48) -> "G1Srs":
+        """BLS12-381 G1 bases (n, 48) compressed -> G1Srs, decoded checked (curve and subgroup) and kept in HBM in the form
+        the bucket kernel gathers.  Raises InvalidData (its .status: 0 / 2 per point) if any point is invalid: no set is
+        made.  The point at infinity is a valid base."""
+        pts = np.ascontiguousarray(points48, dtype=np.uint8).reshape(-1, 48)
+        n = pts.shape[0]
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        h = ctypes.c_void_p()
+        rc = self._lib.vrfhip_g1_srs_create(self._h, n, _ptr(pts) if n else None, _ptr(st), ctypes.byref(h))
+        if rc != 0 and n and st[:n].any():
+            err = InvalidData("invalid base point(s): %s" % np.flatnonzero(st[:n])[:8].tolist())
+            err.status = st[:n]
+            raise err
+        _lib.check(rc, "vrfhip_g1_srs_create")
+        return G1Srs(self, h, n)
+
+    def kzg_commit_batch(self, srs, coeffs, first: int = 0):
+        """`KZG10::commit` for k columns at once: coeffs (k, len, 32) little-endian < r ->
+        (out48 (k, 48), out_xy (k, 96), status (k,)) with out[c] = sum_j coeffs[c][j] srs[first + j]; status 2 (and zeroed
+        outputs) for a column holding a scalar >= r."""
+        c = np.ascontiguousarray(coeffs, dtype=np.uint8)
+        if c.ndim != 3 or c.shape[2] != 32:
+            raise ValueError("coeffs must have shape (k, len, 32)")
+        k, n = c.shape[0], c.shape[1]
+        out, xy, st = np.empty((k, 48), np.uint8), np.empty((k, 96), np.uint8), np.empty(k, np.uint8)
+        _lib.check(self._lib.vrfhip_kzg_commit_batch(self._h, srs.handle, k, n, first, _ptr(c) if c.size else None, _ptr(out),
+                                                     _ptr(xy), _ptr(st)), "vrfhip_kzg_commit_batch")
+        return out, xy, st
+
+    def kzg_commit_batch_dev(self, srs, coeffs, out48, status, first: int = 0, out_xy=None, stream=None):
+        """Device form: tensors coeffs (k, len, 32), out48 (k, 48), status (k,), out_xy (k, 96) optional."""
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _lib.check(self._lib.vrfhip_kzg_commit_batch_dev(self._h, srs.handle, coeffs.shape[0], coeffs.shape[1], first,
+                                                         coeffs.data_ptr() if coeffs.numel() else None, out48.data_ptr(),
+                                                         None if out_xy is None else out_xy.data_ptr(), status.data_ptr(), st),
+                   "vrfhip_kzg_commit_batch_dev")
+
+    def kzg_open_batch(self, srs, coeffs, points):
+        """The non-hiding `KZG10::open` for k polynomials at once: coeffs (k, len, 32) in the monomial basis, points (k, 32)
+        -> (value (k, 32), proof48 (k, 48), proof_xy (k, 96), status (k,)); what kzg_check_batch accepts."""
+        c = np.ascontiguousarray(coeffs, dtype=np.uint8)
+        z = np.ascontiguousarray(points, dtype=np.uint8).reshape(-1, 32)
+        if c.ndim != 3 or c.shape[2] != 32 or z.shape[0] != c.shape[0]:
+            raise ValueError("coeffs must have shape (k, len, 32) and points (k, 32)")
+        k, n = c.shape[0], c.shape[1]
+        v, out, xy, st = np.empty((k, 32), np.uint8), np.empty((k, 48), np.uint8), np.empty((k, 96), np.uint8), np.empty(k, np.uint8)
+        _lib.check(self._lib.vrfhip_kzg_open_batch(self._h, srs.handle, k, n, _ptr(c) if c.size else None, _ptr(z), _ptr(v),
+                                                   _ptr(out), _ptr(xy), _ptr(st)), "vrfhip_kzg_open_batch")
+        return v, out, xy, st
+
+    def kzg_open_batch_dev(self, srs, coeffs, points, value, proof48, status, proof_xy=None, stream=None):
+        """Device form: tensors coeffs (k, len, 32), points / value (k, 32), proof48 (k, 48), status (k,), proof_xy optional."""
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _lib.check(self._lib.vrfhip_kzg_open_batch_dev(self._h, srs.handle, coeffs.shape[0], coeffs.shape[1], coeffs.data_ptr(),
+                                                       points.data_ptr(), value.data_ptr(), proof48.data_ptr(),
+                                                       None if proof_xy is None else proof_xy.data_ptr(), status.data_ptr(), st),
+                   "vrfhip_kzg_open_batch_dev")
+
     @staticmethod
     def _kzg_multi_shape(n, commitments, scalars, shared_bases, shared_scalars, proofs, points, coefs):
         """(k, m, p) from the arrays' second dimensions -- arrays or tensors of shape (n, count, width), None = count 0 --
@@ -1144,6 +1205,24 @@ class KeySet:
     def close(self) -> None:
         if self.handle:
             self._ctx._lib.vrfhip_keyset_destroy(self.handle)
+            self.handle = None
+
+
+class G1Srs:
+    """Device-resident BLS12-381 G1 bases of KZG commitments and openings (vrfhip_g1_srs); destroy before its Context."""
+
+    def __init__(self, ctx: Context, handle, n: int):
+        self._ctx, self.handle, self.n = ctx, handle, n
+
+    def size(self) -> int:
+        return int(self._ctx._lib.vrfhip_g1_srs_size(self.handle))
+
+    def bytes(self) -> int:
+        return int(self._ctx._lib.vrfhip_g1_srs_bytes(self.handle))
+
+    def close(self) -> None:
+        if self.handle:
+            self._ctx._lib.vrfhip_g1_srs_destroy(self.handle)
             self.handle = None
 
 

@@ -172,6 +172,14 @@ struct vrfhip_keyset {
   size_t bytes = 0;
 };
 
+// BLS12-381 G1 bases resident in HBM (KZG commitments and openings)
+struct vrfhip_g1_srs {
+  vrfhip_ctx* ctx = nullptr;
+  size_t n = 0;
+  uint32_t* d_pts = nullptr;      // [n][G1_AFF_STRIDE] Montgomery affine slots (msm_g1.h: G1_SRS_INF_WORD marks infinity)
+  size_t bytes = 0;
+};
+
 namespace {
 
 struct DeviceGuard {
@@ -2284,6 +2292,197 @@ int32_t vrfhip_kzg_check_batch_rlc(vrfhip_ctx* ctx, size_t n, const uint8_t* com
     if (rc) return rc;
   }
   HIP_TRY(hipMemcpyAsync(status, d.st, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+
+// ------------------------------------------------------------------------- KZG commitments and openings (k_kzg_prove.hip)
+int32_t vrfhip_g1_srs_create(vrfhip_ctx* ctx, size_t n, const uint8_t* points48, uint8_t* status, void** out) {
+  if (!out) return fail(VRFHIP_ERR_BAD_ARG, "out is NULL");
+  *out = nullptr;
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
+  if (n == 0 || !points48) return fail(VRFHIP_ERR_BAD_ARG, "no points");
+  if (n > G1_SRS_MAX) return fail(VRFHIP_ERR_BAD_ARG, "too many points (at most 2^20)");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  std::unique_ptr<vrfhip_g1_srs, void (*)(void*)> owner(new vrfhip_g1_srs(), vrfhip_g1_srs_destroy);
+  vrfhip_g1_srs* srs = owner.get();
+  srs->ctx = ctx;
+  srs->n = n;
+  srs->bytes = n * G1_AFF_STRIDE * sizeof(uint32_t);
+  DevTmp<uint8_t> d_in, d_xy, d_st;
+  HIP_TRY(hipMalloc(&srs->d_pts, srs->bytes));
+  HIP_TRY(hipMalloc(&d_in, n * 48));
+  HIP_TRY(hipMalloc(&d_xy, n * 96));
+  HIP_TRY(hipMalloc(&d_st, n));
+  HIP_TRY(hipMemcpyAsync(d_in, points48, n * 48, hipMemcpyHostToDevice, ctx->stream));
+  launch_g1_decode(n, d_in, true, d_xy, d_st, ctx->stream);
+  launch_g1_srs_fill(n, d_xy, d_st, srs->d_pts, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  std::vector<uint8_t> st(n);
+  HIP_TRY(hipMemcpyAsync(st.data(), d_st, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (status) std::memcpy(status, st.data(), n);
+  for (size_t i = 0; i < n; ++i)
+    if (st[i] != VRFHIP_ST_OK) return fail(VRFHIP_ERR_BAD_ARG, "an invalid base point (status names it): no base set is made");
+  *out = owner.release();
+  return VRFHIP_SUCCESS;
+}
+
+void vrfhip_g1_srs_destroy(void* handle) {
+  vrfhip_g1_srs* srs = static_cast<vrfhip_g1_srs*>(handle);
+  if (!srs) return;
+  if (srs->ctx && srs->d_pts) {
+    DeviceGuard guard(srs->ctx->device);
+    (void)hipFree(srs->d_pts);
+  }
+  delete srs;
+}
+size_t vrfhip_g1_srs_size(const void* srs) { return srs ? static_cast<const vrfhip_g1_srs*>(srs)->n : 0; }
+size_t vrfhip_g1_srs_bytes(const void* srs) { return srs ? static_cast<const vrfhip_g1_srs*>(srs)->bytes : 0; }
+int32_t vrfhip_test_g1_msm_groups(vrfhip_ctx* ctx, size_t n, int32_t sets, int32_t windows) {
+  if (!ctx || sets < 1 || windows < 1) return fail(VRFHIP_ERR_BAD_ARG, "NULL ctx or an empty shape");
+  return g1_msm_groups(n ? n : 1, sets, windows, ctx->cus);
+}
+}  // extern "C"
+
+namespace {
+// columns of one launch group: at most KZG_PROVE_GROUP_COLUMNS, and KZG_PROVE_GROUP_SCALARS scalars unless one column has more
+size_t kzg_prove_group(size_t k, size_t len) {
+  size_t kc = len ? KZG_PROVE_GROUP_SCALARS / len : KZG_PROVE_GROUP_COLUMNS;
+  kc = std::max<size_t>(1, std::min(kc, KZG_PROVE_GROUP_COLUMNS));
+  return std::min(kc, k);
+}
+int32_t kzg_prove_args(vrfhip_ctx* ctx, const vrfhip_g1_srs* srs, size_t k) {
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
+  if (!srs || srs->ctx != ctx) return fail(VRFHIP_ERR_BAD_ARG, "base set is NULL or of another context");
+  if (k == 0) return fail(VRFHIP_ERR_BAD_ARG, "k must be at least 1");
+  if (k > (size_t(1) << 28)) return fail(VRFHIP_ERR_BAD_ARG, "batch too large");
+  return VRFHIP_SUCCESS;
+}
+// one launch group of either call: `cols` columns over `pts_n` shared points starting at slot `first`
+struct KzgProveGroup {
+  G1MsmLayout L;
+  uint32_t* wg_sums;
+};
+int32_t kzg_prove_workspace(vrfhip_ctx* ctx, size_t pts_n, size_t cols, size_t q_wgs) {
+  const int groups = g1_msm_groups(pts_n ? pts_n : 1, (int)cols, G1_W_FULL, ctx->cus);
+  return ensure_msm_workspace(ctx, g1_shared_workspace_bytes(pts_n, (int)cols, groups, q_wgs));
+}
+KzgProveGroup kzg_prove_layout(vrfhip_ctx* ctx, const vrfhip_g1_srs* srs, size_t first, size_t pts_n, size_t cols, size_t q_wgs) {
+  KzgProveGroup g;
+  const int groups = g1_msm_groups(pts_n ? pts_n : 1, (int)cols, G1_W_FULL, ctx->cus);
+  g.L = g1_shared_layout(pts_n, (int)cols, groups, q_wgs, ctx->d_msm_ws, srs->d_pts + first * G1_AFF_STRIDE, &g.wg_sums);
+  return g;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t vrfhip_kzg_commit_batch_dev(vrfhip_ctx* ctx, const void* handle, size_t k, size_t len, size_t first,
+                                    const uint8_t* d_coeffs, uint8_t* d_out48, uint8_t* d_out_xy, uint8_t* d_status,
+                                    void* stream) {
+  const vrfhip_g1_srs* srs = static_cast<const vrfhip_g1_srs*>(handle);
+  int32_t rc = kzg_prove_args(ctx, srs, k);
+  if (rc) return rc;
+  if (first > srs->n || len > srs->n - first) return fail(VRFHIP_ERR_BAD_ARG, "first + len exceeds the base set");
+  if ((len && !d_coeffs) || !d_out48 || !d_status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t cap = kzg_prove_group(k, len);
+  rc = kzg_prove_workspace(ctx, len, cap, 0);
+  if (rc) return rc;
+  rc = for_chunks(k, cap, [&](size_t base, size_t m) -> int32_t {
+    const KzgProveGroup g = kzg_prove_layout(ctx, srs, first, len, m, 0);
+    launch_kzg_commit(g.L, at(d_coeffs, base, len * 32), d_out48 + base * 48, at(d_out_xy, base, 96), d_status + base, st,
+                      prof_events(ctx));
+    // the digits, the sorted lists and the partial sums are functions of the (secret) columns
+    if (len) HIP_TRY(hipMemsetAsync(g.L.digits, 0, g1_shared_secret_bytes(g.L), st));
+    return VRFHIP_SUCCESS;
+  });
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return VRFHIP_SUCCESS;
+}
+
+int32_t vrfhip_kzg_commit_batch(vrfhip_ctx* ctx, const void* handle, size_t k, size_t len, size_t first,
+                                const uint8_t* coeffs, uint8_t* out48, uint8_t* out_xy, uint8_t* status) {
+  const vrfhip_g1_srs* srs = static_cast<const vrfhip_g1_srs*>(handle);
+  int32_t rc = kzg_prove_args(ctx, srs, k);
+  if (rc) return rc;
+  if (first > srs->n || len > srs->n - first) return fail(VRFHIP_ERR_BAD_ARG, "first + len exceeds the base set");
+  if ((len && !coeffs) || !out48 || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  uint8_t *d_c, *d_o, *d_xy, *d_st;
+  rc = stage_layout(ctx, [&](Stage& sg) {
+    d_c = sg.take(k * len * 32 + 1); d_o = sg.take(k * 48); d_xy = sg.take(k * 96); d_st = sg.take(k);
+  });
+  if (rc) return rc;
+  if (len) HIP_TRY(hipMemcpyAsync(d_c, coeffs, k * len * 32, hipMemcpyHostToDevice, ctx->stream));
+  rc = vrfhip_kzg_commit_batch_dev(ctx, srs, k, len, first, d_c, d_o, out_xy ? d_xy : nullptr, d_st, ctx->stream);
+  if (len) HIP_TRY(hipMemsetAsync(d_c, 0, k * len * 32, ctx->stream));            // staged columns
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out48, d_o, k * 48, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_xy) HIP_TRY(hipMemcpyAsync(out_xy, d_xy, k * 96, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(status, d_st, k, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+
+int32_t vrfhip_kzg_open_batch_dev(vrfhip_ctx* ctx, const void* handle, size_t k, size_t len, const uint8_t* d_coeffs,
+                                  const uint8_t* d_z, uint8_t* d_value, uint8_t* d_proof48, uint8_t* d_proof_xy,
+                                  uint8_t* d_status, void* stream) {
+  const vrfhip_g1_srs* srs = static_cast<const vrfhip_g1_srs*>(handle);
+  int32_t rc = kzg_prove_args(ctx, srs, k);
+  if (rc) return rc;
+  if (len == 0 || len > srs->n) return fail(VRFHIP_ERR_BAD_ARG, "len must be in 1 .. the size of the base set");
+  if (!d_coeffs || !d_z || !d_value || !d_proof48 || !d_status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t cap = kzg_prove_group(k, len), q_wgs = kzg_cut(len).wgs;
+  rc = kzg_prove_workspace(ctx, len - 1, cap, q_wgs);
+  if (rc) return rc;
+  rc = for_chunks(k, cap, [&](size_t base, size_t m) -> int32_t {
+    const KzgProveGroup g = kzg_prove_layout(ctx, srs, 0, len - 1, m, q_wgs);
+    launch_kzg_open(g.L, g.wg_sums, d_coeffs + base * len * 32, d_z + base * 32, d_value + base * 32, d_proof48 + base * 48,
+                    at(d_proof_xy, base, 96), d_status + base, st, prof_events(ctx));
+    HIP_TRY(hipMemsetAsync(g.L.digits, 0, g1_shared_secret_bytes(g.L), st));      // as in the commitment, and the workgroups' H
+    return VRFHIP_SUCCESS;
+  });
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return VRFHIP_SUCCESS;
+}
+
+int32_t vrfhip_kzg_open_batch(vrfhip_ctx* ctx, const void* handle, size_t k, size_t len, const uint8_t* coeffs,
+                              const uint8_t* z, uint8_t* value, uint8_t* proof48, uint8_t* proof_xy, uint8_t* status) {
+  const vrfhip_g1_srs* srs = static_cast<const vrfhip_g1_srs*>(handle);
+  int32_t rc = kzg_prove_args(ctx, srs, k);
+  if (rc) return rc;
+  if (len == 0 || len > srs->n) return fail(VRFHIP_ERR_BAD_ARG, "len must be in 1 .. the size of the base set");
+  if (!coeffs || !z || !value || !proof48 || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  uint8_t *d_c, *d_z, *d_v, *d_o, *d_xy, *d_st;
+  rc = stage_layout(ctx, [&](Stage& sg) {
+    d_c = sg.take(k * len * 32); d_z = sg.take(k * 32); d_v = sg.take(k * 32);
+    d_o = sg.take(k * 48); d_xy = sg.take(k * 96); d_st = sg.take(k);
+  });
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(d_c, coeffs, k * len * 32, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(d_z, z, k * 32, hipMemcpyHostToDevice, ctx->stream));
+  rc = vrfhip_kzg_open_batch_dev(ctx, srs, k, len, d_c, d_z, d_v, d_o, proof_xy ? d_xy : nullptr, d_st, ctx->stream);
+  HIP_TRY(hipMemsetAsync(d_c, 0, k * len * 32, ctx->stream));                      // staged coefficients
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(value, d_v, k * 32, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(proof48, d_o, k * 48, hipMemcpyDeviceToHost, ctx->stream));
+  if (proof_xy) HIP_TRY(hipMemcpyAsync(proof_xy, d_xy, k * 96, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(status, d_st, k, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return VRFHIP_SUCCESS;
 }

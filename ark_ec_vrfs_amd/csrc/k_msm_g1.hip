@@ -98,6 +98,8 @@ __global__ void __launch_bounds__(128) k_g1_prep_msm(G1MsmLayout L, const uint8_
 constexpr uint32_t G1_NONE = 0xffffffffu;
 constexpr uint32_t G1_IDX_MASK = (1u << G1_IDX_BITS) - 1;
 
+// SHARED_PTS: the sets are columns of scalars over one set of points (msm_g1.h)
+template <bool SHARED_PTS>
 __global__ void __launch_bounds__(G1_BLOCK) k_g1_buckets(G1MsmLayout L) {
   extern __shared__ uint32_t lds[];
   uint32_t* bucket = lds;                                   // [512][42]
@@ -112,7 +114,7 @@ __global__ void __launch_bounds__(G1_BLOCK) k_g1_buckets(G1MsmLayout L) {
   const size_t hi = lo + L.per_group < L.n ? lo + L.per_group : L.n;
   const uint32_t cnt_all = lo < hi ? (uint32_t)(hi - lo) : 0u;
   const int16_t* dig = L.digits + ((size_t)set * L.windows + w) * L.n + lo;
-  const uint32_t* P = L.pts + ((size_t)set * L.n + lo) * G1_AFF_STRIDE;
+  const uint32_t* P = L.pts + ((SHARED_PTS ? (size_t)0 : (size_t)set * L.n) + lo) * G1_AFF_STRIDE;
   uint32_t* list = L.lists + (size_t)wg * L.list_cap;
   uint32_t* heads = L.heads + (size_t)wg * G1_BLOCK * G1_PT_WORDS;
   g1p_store(bucket + t * G1_PT_WORDS, g1_identity());
@@ -345,19 +347,48 @@ G1MsmLayout g1_msm_layout(size_t n, int sets, int windows, int groups, void* ws)
   return L;
 }
 
-void launch_g1_buckets(const G1MsmLayout& L, hipStream_t st) {
+void launch_g1_buckets(const G1MsmLayout& L, hipStream_t st, bool shared_pts) {
   const size_t lds_bytes = ((size_t)G1_BUCKETS * G1_PT_WORDS + 2 * G1_BUCKETS + 16) * 4;      // 90,176 B
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_g1_buckets), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_g1_buckets<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_bytes);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_g1_buckets<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds_bytes);
     attr_set = true;
   }
-  hipLaunchKernelGGL(k_g1_buckets, dim3((unsigned)(L.sets * L.windows * L.groups)), dim3(G1_BLOCK), lds_bytes, st, L);
+  const dim3 grid((unsigned)(L.sets * L.windows * L.groups));
+  if (shared_pts) hipLaunchKernelGGL(k_g1_buckets<true>, grid, dim3(G1_BLOCK), lds_bytes, st, L);
+  else hipLaunchKernelGGL(k_g1_buckets<false>, grid, dim3(G1_BLOCK), lds_bytes, st, L);
 }
 void launch_g1_final(const G1MsmLayout& L, hipStream_t st) {
   hipLaunchKernelGGL(k_g1_final, dim3((unsigned)L.sets), dim3(G1_FINAL_BLOCK), 0, st, L);
 }
+size_t g1_shared_workspace_bytes(size_t n, int sets, int groups, size_t q_wgs) {
+  const size_t per_group = (n + groups - 1) / groups, list_cap = per_group + G1_BLOCK, wgs = (size_t)sets * G1_W_FULL * groups;
+  return pad256((size_t)sets * G1_W_FULL * n * 2) + pad256(wgs * list_cap * 4) + pad256(wgs * G1_BLOCK * G1_PT_WORDS * 4) +
+         pad256(wgs * G1_PT_WORDS * 4) + pad256((size_t)sets * q_wgs * KZG_PART_WORDS * 4) + pad256((size_t)sets * 96) +
+         pad256((size_t)sets);
+}
+G1MsmLayout g1_shared_layout(size_t n, int sets, int groups, size_t q_wgs, void* ws, uint32_t* pts, uint32_t** wg_sums) {
+  G1MsmLayout L;
+  L.n = n; L.sets = sets; L.windows = G1_W_FULL; L.groups = groups;
+  L.per_group = (n + groups - 1) / groups;
+  L.list_cap = L.per_group + G1_BLOCK;
+  const size_t wgs = (size_t)sets * G1_W_FULL * groups;
+  uint8_t* p = static_cast<uint8_t*>(ws);
+  L.pts = pts;
+  L.digits = reinterpret_cast<int16_t*>(p); p += pad256((size_t)sets * G1_W_FULL * n * 2);
+  L.lists = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * L.list_cap * 4);
+  L.heads = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * G1_BLOCK * G1_PT_WORDS * 4);
+  L.part = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * G1_PT_WORDS * 4);
+  *wg_sums = reinterpret_cast<uint32_t*>(p); p += pad256((size_t)sets * q_wgs * KZG_PART_WORDS * 4);
+  L.sums = p; p += pad256((size_t)sets * 96);
+  L.flags = p;
+  return L;
+}
+size_t g1_shared_secret_bytes(const G1MsmLayout& L) { return (size_t)(L.sums - reinterpret_cast<uint8_t*>(L.digits)); }
+
 static void launch_core(const G1MsmLayout& L, hipStream_t st, hipEvent_t* ev) {
   launch_g1_buckets(L, st);
   if (ev) (void)hipEventRecord(ev[1], st);

@@ -48,7 +48,9 @@ void launch_g1_rlc(const G1MsmLayout& L, const uint8_t* g1, const uint8_t seed[3
 void launch_g1_msm(const G1MsmLayout& L, const uint8_t* bases, const uint8_t* scalars, uint8_t* status1, hipStream_t st);
 // The two kernels behind both calls above, for a prep kernel of another unit (k_kzg.hip): the bucket sums of every
 // (set, window, group) of a filled layout, then L.sums.
-void launch_g1_buckets(const G1MsmLayout& L, hipStream_t st);
+// shared_pts: every set reads the SAME n points at L.pts (the columns of a commitment over resident bases) instead of its own
+// n at L.pts + set * n * G1_AFF_STRIDE; a second instantiation of the kernel, the first one is untouched.
+void launch_g1_buckets(const G1MsmLayout& L, hipStream_t st, bool shared_pts = false);
 void launch_g1_final(const G1MsmLayout& L, hipStream_t st);
 
 // G1 codec (k_g1_codec.hip, g1_codec.cuh), one lane per point, no workspace; all arrays 4-byte aligned device memory.
@@ -118,5 +120,45 @@ void launch_kzg_multi_rlc(const G1MsmLayout& A, const G1MsmLayout& B, size_t n, 
                           const KzgMultiArrays& a, const uint8_t* g, const uint8_t* shared_bases, const uint8_t seed[32],
                           const uint8_t* d_root, uint32_t* weights, uint32_t* partials, uint8_t* status, uint8_t* item192,
                           hipStream_t st, hipEvent_t* ev = nullptr);
+
+// KZG commitments and openings over a resident base set (k_kzg_prove.hip, kzg_prove.cuh).
+// A resident base: Montgomery affine (x, y) in a G1_AFF_STRIDE slot as k_g1_buckets gathers it, word G1_SRS_INF_WORD != 0 for
+// the point at infinity (its digits are written as zero, its coordinates are never read).
+constexpr int G1_SRS_INF_WORD = G1_AFF_WORDS;
+constexpr size_t G1_SRS_MAX = size_t(1) << 20;           // points of a base set
+constexpr int KZGQ_BLOCK = 256;                          // lanes per workgroup of k_kzg_quotient
+constexpr int KZGQ_CHUNK_MAX = 16;                       // coefficients per lane before a polynomial takes more workgroups
+// how a polynomial of len coefficients is cut: `chunk` coefficients per lane, `wgs` workgroups of KZGQ_BLOCK lanes.  Up to
+// KZGQ_BLOCK coefficients one per lane; the chunk grows to KZGQ_CHUNK_MAX, then the workgroups multiply (16 at len = 2^16).
+struct KzgCut { uint32_t chunk, wgs; };
+inline KzgCut kzg_cut(size_t len) {
+  KzgCut c;
+  size_t m = (len + KZGQ_BLOCK - 1) / KZGQ_BLOCK;
+  if (m < 1) m = 1;
+  if (m > (size_t)KZGQ_CHUNK_MAX) m = KZGQ_CHUNK_MAX;
+  c.chunk = (uint32_t)m;
+  const size_t per_wg = m * KZGQ_BLOCK;
+  c.wgs = (uint32_t)(len ? (len + per_wg - 1) / per_wg : 1);
+  return c;
+}
+constexpr size_t KZG_PROVE_GROUP_SCALARS = size_t(1) << 20;   // a launch group: at most this many scalars ...
+constexpr size_t KZG_PROVE_GROUP_COLUMNS = 64;                // ... and this many columns (at least one)
+// xy / status: n decoded points and their statuses (launch_g1_decode) -> n slots; an invalid point leaves a zeroed slot
+void launch_g1_srs_fill(size_t n, const uint8_t* g1_xy, const uint8_t* status, uint32_t* slots, hipStream_t st);
+// A layout of `sets` columns over n SHARED points (pts: the first slot), windows = G1_W_FULL, without a point region:
+// digits | lists | heads | part | wg_sums (sets x q_wgs x KZG_PART_WORDS words) | sums (sets x 96 B) | flags (one byte per set).
+// [digits, sums) holds functions of the scalars alone: the callers wipe it (g1_shared_secret_bytes from L.digits).
+size_t g1_shared_workspace_bytes(size_t n, int sets, int groups, size_t q_wgs);
+G1MsmLayout g1_shared_layout(size_t n, int sets, int groups, size_t q_wgs, void* ws, uint32_t* pts, uint32_t** wg_sums);
+size_t g1_shared_secret_bytes(const G1MsmLayout& L);
+// ev (nullable, 5 events): start | prep or quotient | buckets | final | encode.
+// Commit: out[c] = sum_j coeffs[c][j] pts[j], c < L.sets, j < L.n; coeffs: sets x n x 32 B.  out48: sets x 48 B compressed,
+// out_xy (nullable): sets x 96 B, status[c] = 0 / 2 (a scalar >= r: the column's outputs are zeroed).  L.n = 0: infinity.
+void launch_kzg_commit(const G1MsmLayout& L, const uint8_t* coeffs, uint8_t* out48, uint8_t* out_xy, uint8_t* status,
+                       hipStream_t st, hipEvent_t* ev = nullptr);
+// Open: L.sets polynomials of len = L.n + 1 coefficients (coeffs: sets x len x 32 B) at z (sets x 32 B): value (sets x 32 B),
+// proof48 / proof_xy / status as above (status 2 also for z >= r; value is zeroed too).
+void launch_kzg_open(const G1MsmLayout& L, uint32_t* wg_sums, const uint8_t* coeffs, const uint8_t* z, uint8_t* value,
+                     uint8_t* proof48, uint8_t* proof_xy, uint8_t* status, hipStream_t st, hipEvent_t* ev = nullptr);
 
 }  // namespace vrf

@@ -169,7 +169,8 @@ typedef struct vrfhip_keyset vrfhip_keyset;
 
 /* Library / context ------------------------------------------------------------------- */
 
-/* ABI version of this header (major*100 + minor). */
+/* ABI version of this header (major*100 + minor).  vrfhip_g1_srs_*, vrfhip_kzg_commit_batch* and vrfhip_kzg_open_batch* came
+ * in under 146: they only add entry points, nothing that existed changed. */
 int32_t vrfhip_abi_version(void);
 
 /* Last error text for this thread ("" if none). */
@@ -622,6 +623,67 @@ int32_t vrfhip_kzg_check_batch_rlc_dev(vrfhip_ctx* ctx, size_t n, const uint8_t*
                                        const uint8_t* d_values32, const uint8_t* d_proofs48, const uint8_t* d_vk,
                                        const uint8_t seed[32], uint8_t* d_status, uint8_t* d_verdict, uint8_t* d_sums,
                                        void* stream);
+
+/* KZG commitments and openings over a base set that stays on the device -- `KZG10::commit` and the NON-HIDING `KZG10::open` of
+ * ark-poly-commit, the producer side of the checks above.  Both are defined by the arithmetic alone: with bases [tau^j] G the
+ * commitment of p is [p(tau)] G and the proof of p(z) = v is [(p(tau) - v) / (tau - z)] G; with Lagrange bases the same sums
+ * commit to evaluations.  The hiding form (`rand`, `gamma_g`, a blinding polynomial) is out of scope, as are multi-point
+ * openings, basis conversion, the ring's column layout and its transcript.
+ *
+ * vrfhip_g1_srs_create: points48 = n x 48 B (host) in the compressed form vrfhip_g1_decode_batch reads, decoded with the
+ * checked semantics (on the curve and in the subgroup of order r) and kept as Montgomery affine coordinates in 128-byte
+ * slots, the form the bucket kernel gathers: no call below converts, tests or copies a base again.  status (nullable, host,
+ * n bytes): 0 or 2 per point.  If any point is invalid no handle is made (*out = NULL) and the call returns
+ * VRFHIP_ERR_BAD_ARG: a commitment over a partly valid base set means nothing.  The point at infinity (0xC0 00...) is a valid
+ * base and takes no part in any sum.  1 <= n <= 2^20.  The set belongs to the context: destroy it before the context, as a
+ * key set.  _size: n; _bytes: the HBM it holds (128 n).
+ *
+ * vrfhip_kzg_commit_batch*: k columns in one call over the same bases,
+ *     out[c] = sum_{j<len} coeffs[c][j] * srs[first + j],      c < k.
+ * coeffs: k x len x 32 B little-endian, < r; out48: k x 48 B compressed; out_xy (nullable): k x 96 B, x || y little-endian,
+ * all-zero = infinity, the form vrfhip_g1_msm writes.  first + len <= n, else VRFHIP_ERR_BAD_ARG; `first` commits a delta over
+ * a slice of the bases.  len = 0: every result is infinity (0xC0 00...), coeffs may be NULL.  status[c]: 0, or 2 if a scalar
+ * of column c is >= r -- then the 48 (and 96) output bytes of that column are zero and the other columns are unaffected.
+ * k >= 1.  One prep lane per scalar writes signed 10-bit digits; the bucket and final kernels of vrfhip_g1_msm run with
+ * column = set over the shared points.
+ *
+ * vrfhip_kzg_open_batch*: k polynomials of len coefficients each (monomial basis, coeffs[c][j] the coefficient of X^j),
+ * polynomial c opened at z[c]:
+ *     value[c] = p_c(z_c),     proof[c] = sum_{j<len-1} q_j * srs[j],     q = (p_c - value[c]) / (X - z_c),
+ * by the recurrence q_{len-2} = p_{len-1}, q_{j-1} = p_j + z q_j, v = p_0 + z q_0, run as a scan over lanes and workgroups;
+ * the digits of q go straight into the multi-scalar multiplication and the result is bit-identical to the sequential
+ * recurrence.  z, value: k x 32 B little-endian; proof48 / proof_xy (nullable) as out48 / out_xy.  1 <= len <= n; len = 1:
+ * value = p_0, proof = infinity.  status[c] = 2 if a coefficient of polynomial c or z[c] is >= r: value, proof48 and proof_xy
+ * of that polynomial are zero.  (commitment, z, value, proof48) are what vrfhip_kzg_check_batch* accepts.
+ *
+ * Launch groups: a call cuts k into groups of columns, each at most 64 columns and at most 2^20 scalars (one column if len
+ * alone exceeds that), so the workspace (the context's MSM workspace: 52 B of digits and about 104 B of sorted lists per
+ * scalar, 86 KiB per (column, window, point group)) stays below 400 MiB whatever k is.
+ * Secrets: columns and polynomials are witness data upstream.  Before a host form returns -- at the end of the enqueued work
+ * for a _dev form -- the digit, list, head and partial-sum regions of the workspace and the staged coefficients of the host
+ * forms are overwritten with zeros.  The caller's own arrays are the caller's.  NOT constant-time: the bucket sort gathers
+ * by digit, so memory traffic and timing depend on the scalars.
+ * The handle (vrfhip_g1_srs in the text above) is an opaque pointer, spelled void* in the prototypes: *out of _create, srs
+ * everywhere else.
+ * Device arrays 4-byte aligned.  VRFHIP_ERR_UNSUPPORTED on a secp256r1 context; VRFHIP_ERR_BAD_ARG for a NULL handle or one of
+ * another context, k = 0, a slice outside the set, len outside its range, a NULL array that would be read or written. */
+int32_t vrfhip_g1_srs_create(vrfhip_ctx* ctx, size_t n, const uint8_t* points48, uint8_t* status, void** out);
+void vrfhip_g1_srs_destroy(void* srs);
+size_t vrfhip_g1_srs_size(const void* srs);
+size_t vrfhip_g1_srs_bytes(const void* srs);
+/* Test hook: the point groups per (set, window) the G1 multi-scalar multiplication runs on this device for n points -- the
+ * number g1_msm_groups gives every call above (windows: 26 for full scalars, 13 for 128-bit weights).  > 0, or an error. */
+int32_t vrfhip_test_g1_msm_groups(vrfhip_ctx* ctx, size_t n, int32_t sets, int32_t windows);
+int32_t vrfhip_kzg_commit_batch(vrfhip_ctx* ctx, const void* srs, size_t k, size_t len, size_t first,
+                                const uint8_t* coeffs, uint8_t* out48, uint8_t* out_xy, uint8_t* status);
+int32_t vrfhip_kzg_commit_batch_dev(vrfhip_ctx* ctx, const void* srs, size_t k, size_t len, size_t first,
+                                    const uint8_t* d_coeffs, uint8_t* d_out48, uint8_t* d_out_xy, uint8_t* d_status,
+                                    void* stream);
+int32_t vrfhip_kzg_open_batch(vrfhip_ctx* ctx, const void* srs, size_t k, size_t len, const uint8_t* coeffs,
+                              const uint8_t* z, uint8_t* value, uint8_t* proof48, uint8_t* proof_xy, uint8_t* status);
+int32_t vrfhip_kzg_open_batch_dev(vrfhip_ctx* ctx, const void* srs, size_t k, size_t len, const uint8_t* d_coeffs,
+                                  const uint8_t* d_z, uint8_t* d_value, uint8_t* d_proof48, uint8_t* d_proof_xy,
+                                  uint8_t* d_status, void* stream);
 
 /* Multi-commitment, multi-point KZG openings -- the shape a ring proof ends in (as far as upstream is recalled, INTEGRATION.md
  * section 4): the verifier folds its proof's column commitments and fixed columns of its key into aggregate commitments, opens

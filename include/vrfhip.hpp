@@ -670,6 +670,76 @@ std::vector<Result> check_batch_rlc(const Context<S>& ctx, const std::vector<Ope
   for (size_t i = 0; i < n; ++i) r[i] = result_of(st[i]);
   return r;
 }
+
+// The producer side: `KZG10::commit` and the non-hiding `KZG10::open` over bases resident in HBM (vrfhip_g1_srs,
+// vrfhip_kzg_commit_batch, vrfhip_kzg_open_batch).  Scalars are 32-byte little-endian integers below r.
+using Scalar = std::array<uint8_t, 32>;
+using G1Compressed = std::array<uint8_t, 48>;
+template <class S>
+class Srs {
+ public:
+  // throws (Error::InvalidData semantics: no set is made) if any base is not a point of the prime-order subgroup
+  Srs(const Context<S>& ctx, const std::vector<G1Compressed>& bases) : n_(bases.size()) {
+    Bytes flat(48 * n_ + 1);
+    for (size_t i = 0; i < n_; ++i) std::memcpy(flat.data() + 48 * i, bases[i].data(), 48);
+    check(vrfhip_g1_srs_create(ctx.handle(), n_, flat.data(), nullptr, &h_), "vrfhip_g1_srs_create");
+  }
+  ~Srs() { vrfhip_g1_srs_destroy(h_); }
+  Srs(const Srs&) = delete;
+  Srs& operator=(const Srs&) = delete;
+  const void* handle() const { return h_; }            // the opaque vrfhip_g1_srs handle
+  size_t size() const { return vrfhip_g1_srs_size(h_); }
+  size_t bytes() const { return vrfhip_g1_srs_bytes(h_); }
+
+ private:
+  void* h_ = nullptr;
+  size_t n_;
+};
+struct Commitment { G1Compressed point; Result status; };
+struct OpeningProof { Scalar value; G1Compressed proof; Result status; };
+namespace detail_kzg {
+inline Bytes flatten(const std::vector<std::vector<Scalar>>& cols, size_t len) {
+  Bytes flat(cols.size() * len * 32 + 1);
+  for (size_t c = 0; c < cols.size(); ++c) {
+    if (cols[c].size() != len) throw std::invalid_argument("ragged columns");
+    for (size_t j = 0; j < len; ++j) std::memcpy(flat.data() + (c * len + j) * 32, cols[c][j].data(), 32);
+  }
+  return flat;
+}
+}  // namespace detail_kzg
+// out[c] = sum_j columns[c][j] * srs[first + j]; all columns of one length
+template <class S>
+std::vector<Commitment> commit_batch(const Context<S>& ctx, const Srs<S>& srs, const std::vector<std::vector<Scalar>>& columns,
+                                     size_t first = 0) {
+  const size_t k = columns.size(), len = k ? columns[0].size() : 0;
+  const Bytes flat = detail_kzg::flatten(columns, len);
+  Bytes out(48 * k + 1), st(k + 1);
+  check(vrfhip_kzg_commit_batch(ctx.handle(), srs.handle(), k, len, first, flat.data(), out.data(), nullptr, st.data()),
+        "vrfhip_kzg_commit_batch");
+  std::vector<Commitment> r(k);
+  for (size_t c = 0; c < k; ++c) { std::memcpy(r[c].point.data(), out.data() + 48 * c, 48); r[c].status = result_of(st[c]); }
+  return r;
+}
+// polynomial c (monomial basis) opened at points[c]: value and proof, what check_batch accepts
+template <class S>
+std::vector<OpeningProof> open_batch(const Context<S>& ctx, const Srs<S>& srs, const std::vector<std::vector<Scalar>>& polys,
+                                     const std::vector<Scalar>& points) {
+  const size_t k = polys.size(), len = k ? polys[0].size() : 0;
+  if (points.size() != k) throw std::invalid_argument("one point per polynomial");
+  const Bytes flat = detail_kzg::flatten(polys, len);
+  Bytes z(32 * k + 1), v(32 * k + 1), out(48 * k + 1), st(k + 1);
+  for (size_t c = 0; c < k; ++c) std::memcpy(z.data() + 32 * c, points[c].data(), 32);
+  check(vrfhip_kzg_open_batch(ctx.handle(), srs.handle(), k, len, flat.data(), z.data(), v.data(), out.data(), nullptr,
+                              st.data()),
+        "vrfhip_kzg_open_batch");
+  std::vector<OpeningProof> r(k);
+  for (size_t c = 0; c < k; ++c) {
+    std::memcpy(r[c].value.data(), v.data() + 32 * c, 32);
+    std::memcpy(r[c].proof.data(), out.data() + 48 * c, 48);
+    r[c].status = result_of(st[c]);
+  }
+  return r;
+}
 }  // namespace kzg
 
 }  // namespace ark_vrf_hip
