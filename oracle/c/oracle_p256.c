@@ -413,6 +413,10 @@ int p256_pedersen_prove(const uint8_t sk_be[32], const uint8_t* msg, size_t msg_
   challenge(c, encs, lens, ad, ad_len);
   n_muladd(s, c, sk, k); n_muladd(sb, c, b, kb);
   store_be(s_be, s); store_be(sb_be, sb);
+  /* the point at infinity (sk = 0: Gamma) goes out as 33 zero bytes, as p256_ietf_prove writes it */
+  uint8_t* outs[4] = {pk_com, gamma, r_out, ok_out};
+  const size_t out_lens[4] = {lens[0], lens[2], lens[3], lens[4]};
+  for (int j = 0; j < 4; ++j) if (out_lens[j] != 33) memset(outs[j] + 1, 0, 32);
   if (blinding_out) store_be(blinding_out, b);
   if (h_out) memcpy(h_out, henc, 33);
   return 0;

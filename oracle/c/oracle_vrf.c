@@ -605,7 +605,9 @@ int oracle_ietf_prove(const uint8_t sk_le[32], const uint8_t* msg, size_t msg_le
   uint8_t pts[5][32];
   if (h_given) {
     if (!point_decode_chk(&x, &y, h_given, 2)) return 2;
-    pt_from_affine(&H, &x, &y); memcpy(pts[1], h_given, 32);
+    /* enc(H) of the typed point: a neutral H handed over with the sign bit of x = 0 set decodes, as in arkworks,
+     * and is hashed and returned in its canonical encoding */
+    pt_from_affine(&H, &x, &y); point_encode(pts[1], &x, &y);
   }
   else { hash_to_curve(&H, msg, msg_len); pt_to_affine(&x, &y, &H); point_encode(pts[1], &x, &y); pt_from_affine(&H, &x, &y); }
   pt_from_affine(&G, &BS_GX_M, &BS_GY_M);
@@ -672,7 +674,7 @@ int oracle_pedersen_prove(const uint8_t sk_le[32], const uint8_t* msg, size_t ms
   uint8_t pts[5][32];
   if (h_given) {
     if (!point_decode_chk(&x, &y, h_given, 2)) return 2;
-    memcpy(pts[1], h_given, 32);
+    point_encode(pts[1], &x, &y);                /* enc(H) of the typed point, as in oracle_ietf_prove */
   } else { hash_to_curve(&H, msg, msg_len); pt_to_affine(&x, &y, &H); point_encode(pts[1], &x, &y); }
   pt_from_affine(&H, &x, &y);
   pt_from_affine(&G, &BS_GX_M, &BS_GY_M); pt_from_affine(&B, &BS_BX_M, &BS_BY_M);

@@ -150,6 +150,69 @@ int hb_pedersen_verify_c(uint32_t challenge_len, uint32_t check_mask, const uint
   }
   return (int)host_pedersen_ladders_c<BswS>(T, valid, tabs.data(), pts.data(), c, s, sb);
 }
+// Either prover from a given H as k_bsw.hip stages it: k_bsw_prove_prepare (its given-H branch), the Edwards suite's stage 2
+// (prove_mul_item on the scalar k_prove_mul zeroes when it is not canonical, with its CT switch), k_bsw_prove_finish (bsw_frac of
+// the four products, ONE fixed-shape inversion, the zeroed outputs of a refused item).  Returns the status (0, or 2).
+// out: gamma 33 | c 32 | s 32 | pk (pk_com) 33 | h 33 | r 33 | ok 33 | sb 32 | blinding 32  (293 B; what a scheme lacks stays zero)
+int hb_prove_cases(int pedersen, int ct, uint32_t check_mask, const uint8_t* sk_, const uint8_t* h_given, const uint8_t* ad,
+                   uint32_t ad_len, uint8_t* o) {
+  static std::vector<uint32_t> combs[2];                   // generator, blinding base: by the device's own builder
+  if (combs[0].empty()) {
+    std::vector<uint32_t> prefix((size_t)GC_SEG * NL);
+    for (int which = 0; which < 2; ++which) {
+      combs[which].assign(GCOMB_WORDS, 0);
+      for (int w = 0; w < GC_ROWS; ++w)
+        for (int seg = 0; seg < GC_SEGS; ++seg)
+          gcomb_build_segment<BswS>(combs[which].data(), prefix.data(), which ? BswS::bx() : BswS::gx(), which ? BswS::by() : BswS::gy(), w, seg);
+    }
+  }
+  DevTables T{};
+  T.sq = tables();
+  T.g_comb = combs[0].data(); T.b_comb = combs[1].data();
+  memset(o, 0, 293);
+  uint32_t sk[8], k[8], b[8] = {0}, kb[8] = {0};
+  memcpy(sk, sk_, 32);
+  bool valid = fr_is_canonical<BswS>(sk);
+  FeN x, y;
+  const Enc33 e = load33(h_given, 0);
+  valid = bsw_decode<BswS>(x, y, e, T.sq) && valid;
+  if (check_mask & CHK_INPUT) valid = in_prime_subgroup<BswS>(x, y, T.sq) && valid;
+  const Enc33 h_enc = enc33_canonical(e);
+  bsw_nonce(k, sk, h_enc);
+  std::vector<uint32_t> tab(ProveLayout<BswS>::TAB_WORDS), pts(PROVE_PTS_WORDS);
+  build_prove_tables<BswS>(tab.data(), x, y);
+  if (pedersen) { bsw_blinding(b, sk, h_enc, ad, ad_len, T.sq.str); bsw_nonce(kb, b, h_enc); }
+  for (int half = 0; half < 2; ++half) {
+    uint32_t sc[8];
+    memcpy(sc, half ? k : sk, 32);
+    if (!fr_is_canonical<BswS>(sc)) memset(sc, 0, 32);
+    const uint32_t* s2 = pedersen ? (half ? kb : b) : nullptr;
+    if (ct) prove_mul_item<BswS, true>(pts.data() + half * 2 * UV_WORDS, T, tab.data(), sc, s2);
+    else prove_mul_item<BswS, false>(pts.data() + half * 2 * UV_WORDS, T, tab.data(), sc, s2);
+  }
+  SwFrac f[4];
+  FeN dens[4], inv[4];
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t* q = pts.data() + j * UV_WORDS;
+    f[j] = bsw_frac<BswS>(fe_load<1, 5>(q), fe_load<1, 5>(q + NL), fe_load<1, 5>(q + 2 * NL));
+    dens[j] = f[j].den;
+  }
+  fe_batch_inv<true>(inv, dens);
+  Enc33 en[4];
+  for (int j = 0; j < 4; ++j) en[j] = bsw_encode_frac(f[j], inv[j]);
+  const Enc33 cp[5] = {en[1], h_enc, en[0], en[3], en[2]};      // pk (or pk_com), H, Gamma, k*G (+ kb*B), k*H
+  uint32_t c[8], cs[8], s[8], sb[8] = {0};
+  bsw_challenge5(c, cp, ad, ad_len, T.sq.str);
+  fr_mul<BswS>(cs, c, sk);
+  fr_add<BswS>(s, cs, k);
+  if (pedersen) { uint32_t cb[8]; fr_mul<BswS>(cb, c, b); fr_add<BswS>(sb, cb, kb); }
+  if (!valid) { memset(c, 0, 32); memset(s, 0, 32); memset(sb, 0, 32); memset(b, 0, 32); }
+  store33(o, 0, en[0], valid); store33(o + 97, 0, en[1], valid); store33(o + 130, 0, h_enc);
+  if (pedersen) { store33(o + 163, 0, en[3], valid); store33(o + 196, 0, en[2], valid); memcpy(o + 229, sb, 32); memcpy(o + 261, b, 32); }
+  else memcpy(o + 33, c, 32);
+  memcpy(o + 65, s, 32);
+  return valid ? 0 : 2;
+}
 void hb_canonical(const uint8_t* enc, uint8_t* o) { store33(o, 0, enc33_canonical(load33(enc, 0))); }
 void hb_challenge(const uint8_t* pts, const uint8_t* ad, uint32_t ad_len, uint8_t* c) {
   Enc33 e[5];

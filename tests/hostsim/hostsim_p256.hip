@@ -218,4 +218,36 @@ int hp_ped_verify_c(uint32_t challenge_len, const uint8_t* h, const uint8_t* gam
   const bool e2 = p256_ped_verify_eq_g(comb().data(), g_comb_b.data(), tp.data(), 1, x[3], y[3], s, sb, c, cw);
   return (e1 && e2) ? 0 : 1;
 }
+// Either prover from a given H as k_p256.hip stages it (k_p256_prove_prepare, _tables, _mul with the ct switch of sw_quad_mul,
+// _finish with the zeroed outputs of a refused item).  Returns the status (0, or 2 = InvalidData).
+// out: gamma 33 | c 32 | s 32 | pk (pk_com) 33 | h 33 | r 33 | ok 33 | sb 32 | blinding 32  (293 B; what a scheme lacks stays zero)
+int hp_prove_cases(int pedersen, int ct, const uint8_t* sk_be, const uint8_t* h_given, const uint8_t* ad, uint32_t ad_len, uint8_t* o) {
+  memset(o, 0, 293);
+  uint32_t sk[8], k[8], b[8], kb[8]; FeN hx, hy; Sec1W henc;
+  if (!p256_prove_prepare_item(sk, k, hx, hy, henc, sk_be, nullptr, 0, h_given, g_str)) return 2;
+  std::vector<uint32_t> tab(SW_QUAD_TABLES * SW_TABLE_WORDS);
+  sw_build_quad_tables(tab.data(), 1, hx, hy);
+  PtW res[4] = {sw_comb_mul(comb().data(), sk), sw_quad_mul(tab.data(), 1, sk, ct != 0), sw_comb_mul(comb().data(), k),
+                sw_quad_mul(tab.data(), 1, k, ct != 0)};
+  uint32_t c[8] = {0}, s[8], sb[8];
+  if (pedersen) {
+    p256_blinding(b, sk, henc, ad, ad_len, g_str);
+    p256_nonce(kb, b, henc.tag, henc.xw);
+    res[0] = sw_add(res[0], sw_comb_mul(g_comb_b.data(), b));
+    res[2] = sw_add(res[2], sw_comb_mul(g_comb_b.data(), kb));
+    Sec1W enc[4];
+    p256_ped_prove_finish_item(enc, s, sb, res, henc, sk, k, b, kb, ad, ad_len, g_str);
+    sec1_store(o, enc[1].tag, enc[1].xw); sec1_store(o + 97, enc[0].tag, enc[0].xw);
+    sec1_store(o + 163, enc[2].tag, enc[2].xw); sec1_store(o + 196, enc[3].tag, enc[3].xw);
+    store_be256(o + 229, sb); store_be256(o + 261, b);
+  } else {
+    Sec1W pk, gamma;
+    p256_prove_finish_item(pk, gamma, c, s, res, henc, sk, k, ad, ad_len, g_str);
+    sec1_store(o, gamma.tag, gamma.xw); sec1_store(o + 97, pk.tag, pk.xw);
+    store_be256(o + 33, c);
+  }
+  store_be256(o + 65, s);
+  sec1_store(o + 130, henc.tag, henc.xw);
+  return 0;
+}
 }

@@ -37,6 +37,7 @@ struct HostTables {
 HostTables& HT() { static HostTables h; h.t.sq.str = g_hs_str; return h; }      // strings may change between calls
 }
 #include "pedersen_c.inc"
+#include "prove_cases.inc"
 static uint32_t g_check_mask_p = 0;    // CHK_* bits for the decode stages (0 = on-curve only)
 extern "C" {
 void hs_set_check_mask_prove(uint32_t m) { g_check_mask_p = m; }
@@ -113,6 +114,11 @@ uint32_t hs_pedersen_verify(const uint8_t* h, const uint8_t* g, const uint8_t* p
 uint32_t hs_pedersen_verify_c(uint32_t challenge_len, const uint8_t* h, const uint8_t* g, const uint8_t* pk_com, const uint8_t* r,
                               const uint8_t* ok, const uint8_t* c, const uint8_t* s, const uint8_t* sb) {
   return host_pedersen_verify_c<SuiteBS>(HT().t, challenge_len, g_check_mask_p, h, g, pk_com, r, ok, c, s, sb);
+}
+// the provers over a batch as k_prove.hip stages them (prove_cases.inc): K proofs per lane, given inputs or messages, both schemes
+void hs_prove_cases(int K, int pedersen, int ct, uint32_t n, const uint8_t* sk, const uint8_t* msgs, uint32_t msg_len,
+                    const uint8_t* inputs, const uint8_t* ad, uint32_t ad_len, uint8_t* out, uint8_t* status) {
+  host_prove_cases<SuiteBS>(HT().t, K, pedersen != 0, ct != 0, n, sk, msgs, msg_len, inputs, ad, ad_len, g_check_mask_p, out, status);
 }
 // batch prove through the K-per-lane prepare, exactly as the kernels run it; out: n x (gamma | c | s | pk | h)
 void hs_ietf_prove_multi(uint32_t n, const uint8_t* sk, const uint8_t* msgs, uint32_t msg_len, const uint8_t* ad,

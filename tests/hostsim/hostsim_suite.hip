@@ -51,6 +51,7 @@ template <int L, int V> static void out(uint8_t* b, const Fe<L, V>& a) { uint32_
 }
 #include "verify_uv.inc"
 #include "pedersen_c.inc"
+#include "prove_cases.inc"
 static uint32_t g_check_mask_x = 0;   // CHK_* bits for the decode stages (0 = on-curve only)
 extern "C" {
 void hx_set_check_mask(uint32_t m) { g_check_mask_x = m; }
@@ -187,6 +188,11 @@ int hx_prove(int pedersen, const uint8_t* sk, const uint8_t* msg, uint32_t len, 
     memcpy(outp, o[0], 32); memcpy(outp + 32, o[1], 32); memcpy(outp + 64, o[2], 32); memcpy(outp + 96, o[3], 32); memcpy(outp + 128, h_enc, 32);
   }
   return valid;
+}
+// the provers over a batch as k_prove.hip stages them (prove_cases.inc): K proofs per lane, given inputs or messages, both schemes
+void hx_prove_cases(int K, int pedersen, int ct, uint32_t n, const uint8_t* sk, const uint8_t* msgs, uint32_t msg_len,
+                    const uint8_t* inputs, const uint8_t* ad, uint32_t ad_len, uint8_t* out, uint8_t* status) {
+  host_prove_cases<SX>(HX().t, K, pedersen != 0, ct != 0, n, sk, msgs, msg_len, inputs, ad, ad_len, g_check_mask_x, out, status);
 }
 uint32_t hx_ietf_verify(const uint8_t* pk, const uint8_t* h, const uint8_t* g, const uint8_t* c, const uint8_t* s,
                         const uint8_t* ad, uint32_t ad_len) {
