@@ -216,6 +216,9 @@ int32_t alloc_workspace(vrfhip_ctx* ctx, size_t cap) {
   size_t total = tabs_b + pts_b + aux_b + flags_b;
   HIP_TRY(hipMalloc(&ctx->d_ws, total));
   uint8_t* p = static_cast<uint8_t*>(ctx->d_ws);
+  // tabs first: an item's region (a multiple of 128 bytes) then starts on a 128-byte line of the allocation, which the
+  // affine JT_VA entries of the GLV verifier rely on for one line per lookup (vrf_core.cuh JT_VA_STRIDE)
+  static_assert((WS_TABS * WIN_TABLE_WORDS * sizeof(uint32_t)) % 128 == 0, "an item's table region is whole 128-byte lines");
   ctx->ws.tabs = reinterpret_cast<uint32_t*>(p); p += tabs_b;
   ctx->ws.pts = reinterpret_cast<uint32_t*>(p); p += pts_b;
   ctx->ws.aux = reinterpret_cast<uint32_t*>(p); p += aux_b;

@@ -267,6 +267,42 @@ VRF_HD int scalar_bit_128(const uint32_t k[4], int bit) {
     if ((bit >> 5) == i) word = k[i];
   return (int)((word >> (bit & 31)) & 1u);
 }
+// Sign-aligned recoding of four magnitudes below 2^127 (GLV-SAC; the V ladder of vrf_core.cuh walks it).  The first one,
+// made odd (a = k0 | 1; `fix` says that this added 1, which the ladder takes back), is written with 128 digits +-1:
+// a = sum d_i 2^i, d_127 = +1, d_i = 2 a_(i+1) - 1 below (a_i the bits of a) -- bit i of `sgn` is set where d_i = -1,
+// i.e. sgn = ~(a >> 1) on bits 0..126.  Every other k_j gets digits in {0, d_i}: bit i of u[j - 1] is set where the digit
+// is d_i.  Digit by digit that is "take k mod 2, subtract the digit, halve", which adds 1 after the halving exactly where
+// the bit was taken with d_i = -1: the carries of the binary addition k + sgn, so u = (k + sgn) ^ sgn, bit 127 being the
+// carry out of bit 126.  128 digits and no fewer: the halving leaves k' - 1 <= (k - 1) / 2, so after 127 of them a
+// k < 2^127 is down to 0 or 1, which the top digit d_127 = +1 can take; after 126 a 2 can be left (k = 2^127 - 1 against
+// a = 1), which it cannot.
+struct SacV {
+  uint32_t sgn[4];
+  uint32_t u[3][4];
+  bool fix;
+};
+VRF_HD void glv_recode_sac(SacV& r, const uint32_t (&m)[4][4]) {
+  r.fix = (m[0][0] & 1u) == 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r.sgn[i] = ~((m[0][i] >> 1) | (i < 3 ? m[0][i + 1] << 31 : 0u));
+  r.sgn[3] &= 0x7fffffffu;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint64_t x = (uint64_t)m[j + 1][i] + r.sgn[i] + c;
+      r.u[j][i] = (uint32_t)x ^ r.sgn[i];
+      c = (uint32_t)(x >> 32);
+    }
+  }
+}
+// digit `bit` (0..127): the JT_V entry (0..7) it selects; sac_neg: whether the entry is subtracted
+VRF_HD int sac_index(const SacV& r, int bit) {
+  return scalar_bit_128(r.u[0], bit) | (scalar_bit_128(r.u[1], bit) << 1) | (scalar_bit_128(r.u[2], bit) << 2);
+}
+VRF_HD bool sac_neg(const SacV& r, int bit) { return scalar_bit_128(r.sgn, bit) != 0; }
+
 // Signed radix-4 recoding of a 128-bit magnitude below 2^127: k + 0x55..5 has the 2-bit fields (d_w + 1) with d_w in
 // [-1, 2] and sum d_w 4^w = k (a field 3 becomes -1 and carries into the next one).  k < 2^127 keeps the sum below 2^128:
 // the top digit cannot carry out.

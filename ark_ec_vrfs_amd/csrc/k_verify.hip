@@ -8,13 +8,13 @@ VRF_NS_BEGIN
 // load_cs_reduced (the proof's scalars as the ladders take them): vrf_core.cuh
 
 // stage 1: one lane per proof.  Decompress pk, H, Gamma; build their window tables -- the GLV suite: the joint tables of
-// -c*Y and of V = s*H - c*Gamma (vrf_core.cuh JT_Y, JT_V; the latter takes the proof's c and s), the other suites: one
+// -c*Y and of V = s*H - c*Gamma (vrf_core.cuh JT_Y, JT_VA; the latter takes the proof's c and s), the other suites: one
 // radix-16 table per point.  A lane's proofs (a.k_decode of them) share nothing: every point has its own inverse root.
 template <class S, int MINW>
 __global__ void __launch_bounds__(BLOCK, MINW) k_verify_decode(VerifyArgs a) {
   size_t first = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * a.k_decode;
   if (first >= a.n) return;
-  verify_decode_multi<S, 3, false, S::HAS_GLV>(a.k_decode, a.T, first, a.n, a.pk, a.h, a.gamma, a.ws.tabs, a.ws.pts, a.ws.flags,
+  verify_decode_multi<S, 3, false, S::HAS_GLV, S::HAS_GLV>(a.k_decode, a.T, first, a.n, a.pk, a.h, a.gamma, a.ws.tabs, a.ws.pts, a.ws.flags,
                                                a.check_mask, a.c, a.s);
 }
 
@@ -44,7 +44,7 @@ template <class S, int MINW>
 __global__ void __launch_bounds__(BLOCK, MINW) k_verify_decode_skip_h(VerifyArgs a) {
   size_t first = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * a.k_decode;
   if (first >= a.n) return;
-  verify_decode_multi<S, 2, true, S::HAS_GLV>(a.k_decode, a.T, first, a.n, a.pk, nullptr, a.gamma, a.ws.tabs, a.ws.pts,
+  verify_decode_multi<S, 2, true, S::HAS_GLV, S::HAS_GLV>(a.k_decode, a.T, first, a.n, a.pk, nullptr, a.gamma, a.ws.tabs, a.ws.pts,
                                               a.ws.flags, a.check_mask, a.c, a.s);
 }
 
@@ -53,7 +53,7 @@ template <class S, int MINW>
 __global__ void __launch_bounds__(BLOCK, MINW) k_verify_decode_keyed(VerifyArgs a) {
   size_t first = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * a.k_decode;
   if (first >= a.n) return;
-  verify_decode_multi<S, 2, false, S::HAS_GLV>(a.k_decode, a.T, first, a.n, nullptr, a.h, a.gamma, a.ws.tabs, a.ws.pts,
+  verify_decode_multi<S, 2, false, S::HAS_GLV, S::HAS_GLV>(a.k_decode, a.T, first, a.n, nullptr, a.h, a.gamma, a.ws.tabs, a.ws.pts,
                                                a.ws.flags, a.check_mask, a.c, a.s);
 #pragma unroll 1
   for (int k = 0; k < a.k_decode; ++k) {
@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(BLOCK) k_verify_decode_affine(VerifyArgs a) {
     load32(c, a.c, i); load32(s, a.s, i);
     load_cs_reduced<S>(c, s);
   }
-  bool ok = verify_decode_affine_item<S, S::HAS_GLV>(enc, xy, a.ws.tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS), a.T.sq,
+  bool ok = verify_decode_affine_item<S, S::HAS_GLV, S::HAS_GLV>(enc, xy, a.ws.tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS), a.T.sq,
                                                      a.check_mask, a.affine_in == 2, c, s);
   uint32_t* aux = a.ws.aux + i * AUX_WORDS;
 #pragma unroll
@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(BLOCK) k_verify_straus(VerifyArgs a) {
   load_cs_reduced<S>(c, s);
   uint32_t* out = a.ws.pts + i * PROVE_PTS_WORDS + HALF * UV_WORDS;
   const uint32_t* tabs = a.ws.tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS);
-  if constexpr (S::HAS_GLV) verify_joint_item<S, HALF>(out, a.T, tabs, c, s);
+  if constexpr (S::HAS_GLV) verify_joint_item<S, HALF, true>(out, a.T, tabs, c, s);
   else verify_straus_item<S, HALF>(out, a.T, tabs, c, s);
 }
 
@@ -130,8 +130,8 @@ __global__ void __launch_bounds__(BLOCK) k_verify_straus_both(VerifyArgs a) {
   load_cs_reduced<S>(c, s);
   const uint32_t* tabs = a.ws.tabs + i * (VERIFY_TABS * WIN_TABLE_WORDS);
   if constexpr (S::HAS_GLV) {
-    if (blockIdx.y == 0) verify_joint_item<S, 1>(a.ws.pts + i * PROVE_PTS_WORDS + UV_WORDS, a.T, tabs, c, s);
-    else verify_joint_item<S, 0>(a.ws.pts + i * PROVE_PTS_WORDS, a.T, tabs, c, s);
+    if (blockIdx.y == 0) verify_joint_item<S, 1, true>(a.ws.pts + i * PROVE_PTS_WORDS + UV_WORDS, a.T, tabs, c, s);
+    else verify_joint_item<S, 0, true>(a.ws.pts + i * PROVE_PTS_WORDS, a.T, tabs, c, s);
   } else {
     if (blockIdx.y == 0) verify_straus_item<S, 1>(a.ws.pts + i * PROVE_PTS_WORDS + UV_WORDS, a.T, tabs, c, s);
     else verify_straus_item<S, 0>(a.ws.pts + i * PROVE_PTS_WORDS, a.T, tabs, c, s);

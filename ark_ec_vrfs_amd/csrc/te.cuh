@@ -236,8 +236,9 @@ VRF_HD PtA pta_identity() {
   return a;
 }
 
+// need_t as in te_add_cached
 template <class C, bool CHAIN = false>
-VRF_HD PtE te_add_affine(const PtE& p, const PtA& q, bool neg) {
+VRF_HD PtE te_add_affine(const PtE& p, const PtA& q, bool neg, bool need_t = true) {
   auto X2 = fe_cneg(neg, q.x);                        // (2,4)
   auto dT2 = fe_cneg(neg, q.dt);                      // (2,4)
   auto Cc = fe_mul<CHAIN>(p.T, dT2);                         // (1,2)
@@ -249,7 +250,8 @@ VRF_HD PtE te_add_affine(const PtE& p, const PtA& q, bool neg) {
   r.X = fe_mul<CHAIN>(E, F);                                 // V 18 -> (1,2)
   r.Y = fe_mul<CHAIN>(G, H);                                 // V <= 21 -> (1,2)
   r.Z = fe_mul<CHAIN>(F, G);                                 // L 6, V 63 -> (1,2)
-  r.T = fe_mul<CHAIN>(E, H);                                 // V <= 6 -> (1,2)
+  r.T = fe_zero();
+  if (need_t) r.T = fe_mul<CHAIN>(E, H);                     // V <= 6 -> (1,2)
   return r;
 }
 

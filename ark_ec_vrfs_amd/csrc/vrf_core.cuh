@@ -156,6 +156,27 @@ VRF_HD bool decode_by_inv_root(Fe<1, 4>& x_out, const DecodeA& a, const SqrtTabl
   const bool sq = fe_inv_sqrt(ir, fe_mul(a.num, a.den), T);
   return decode_finish_x(x_out, a, fe_mul(a.num, ir), sq, T);
 }
+// The same with a second inversion riding on the walk where `ride` is set (uniform over the wave at the call site: the
+// branches are scalar, the walk has one call site): the radicand is m P^2 with m = num den, so the walk gives
+// r = 1 / (sqrt(m) P), whence 1 / sqrt(m) = r P and 1 / P = r m (r P) = r^2 m P -- whichever root the walk took.  P != 0
+// leaves the quadratic character, hence the verdict and x, as they were.  num = 0 (x = 0) rides with m = 1.  pinv is 0 for
+// P = 0 and means nothing where the point is rejected for want of a root.
+template <class C>
+VRF_HD bool decode_by_inv_root_ride(Fe<1, 4>& x_out, FeN& pinv, bool ride, const FeN& P, const DecodeA& a, const SqrtTables& T) {
+  FeN w = fe_mul(a.num, a.den), m = w;
+  if (ride) {
+    m = fe_select(fe_is_zero(w), fe_one(), w);
+    w = fe_mul(m, fe_sqr(P));
+  }
+  FeN ir;
+  const bool sq = fe_inv_sqrt(ir, w, T);
+  if (ride) {
+    const FeN rp = fe_mul(ir, P);
+    pinv = fe_mul(fe_mul(ir, m), rp);
+    ir = rp;
+  }
+  return decode_finish_x(x_out, a, fe_mul(a.num, ir), sq, T);
+}
 
 // Prime-order subgroup membership of a decoded curve point by 2-descent, for curves with full rational
 // 2-torsion and cofactor 4 (Bandersnatch): the subgroup is 2E, and on the Montgomery model
@@ -808,18 +829,34 @@ VRF_HD void load_cs_reduced(uint32_t c[8], uint32_t s[8]) {
 // cost to build.  An item's region of VERIFY_TABS * WIN_TABLE_WORDS words holds, as cached entries (PtC):
 //   JT_Y: the 12 sums a*Y + b*psi(Y), (a, b) = (1,0) (2,0) (0,1) (0,2) (1,+-1) (1,+-2) (2,+-1) (2,+-2): every pair of signed
 //         radix-4 digits in {-1, 0, 1, 2} up to a common sign (joint_y_index).  Independent of the proof's scalars.
-//   JT_V: the 15 non-empty subset sums of Q0 = -/+Gamma, Q1 = -/+psi(Gamma), Q2 = +/-H, Q3 = +/-psi(H), each base with the
-//         sign of its GLV half in V = s*H - c*Gamma; entry m - 1 = sum of Q_t over the set bits t of m.
-// and, behind them, what only the decode stage reads: the extended coordinates the next additions start from, and the affine
-// H and Gamma until both are there.
-constexpr int JT_Y_ENTRIES = 12, JT_V_ENTRIES = 15;
+//   JT_VA: as AFFINE entries (PtA: x, y, d*x*y; JT_VA_STRIDE words apart, so that an entry is one 128-byte line) the 8 sums
+//         Q0 + u1 Q1 + u2 Q2 + u3 Q3, u in {0,1}^3, entry u1 + 2 u2 + 4 u3, of Q0 = -/+Gamma, Q1 = -/+psi(Gamma), Q2 = +/-H,
+//         Q3 = +/-psi(H), each base with the sign of its GLV half in V = s*H - c*Gamma.  The ladder walks the sign-aligned
+//         digits of the four halves (fr.cuh glv_recode_sac): every digit adds or subtracts one entry.
+// and, behind them, what only the decode stage reads: the extended coordinates of the V entries until their common inverse
+// is there (JT_VEXT; the products of their Z coordinates in JT_VPFX, the whole product P in its slot 0), those of Y and 2Y,
+// and the affine H and Gamma until both are there.
+//   JT_V: the form V's table had before (VA = false in the functions below, which no kernel instantiates): the 15 non-empty
+//         subset sums of Q0..Q3 as cached entries, entry m - 1 = sum of Q_t over the set bits t of m, walked bit by bit.  It
+//         stays as the second implementation that tests/hostsim_joint builds and its tests pin entry by entry; it lies over
+//         the words that only the affine form uses.
+constexpr int JT_Y_ENTRIES = 12, JT_VA_ENTRIES = 8, JT_V_ENTRIES = 15;
+constexpr int JT_VA_STRIDE = 32;
 constexpr int JT_Y = 0;
-constexpr int JT_V = JT_Y + JT_Y_ENTRIES * PTC_WORDS;        // word 432
-constexpr int JT_EXT = JT_V + JT_V_ENTRIES * PTC_WORDS;      // word 972: X, Y, Z, T of V entries 1..8 (8 is written, not read)
-constexpr int JT_YEXT = JT_EXT + 8 * PTC_WORDS;              // X, Y, Z, T of Y and 2Y
-constexpr int JT_HXY = JT_YEXT + 2 * PTC_WORDS;              // affine x, y of H
-constexpr int JT_GXY = JT_HXY + 2 * NL;                      // affine x, y of Gamma
-static_assert(JT_GXY + 2 * NL <= VERIFY_TABS * WIN_TABLE_WORDS, "the joint tables and their parking fit the item's region");
+constexpr int JT_VA = 448;                                     // the first 128-byte line behind JT_Y (which ends at word 432)
+constexpr int JT_VEXT = JT_VA + JT_VA_ENTRIES * JT_VA_STRIDE;  // word 704: X, Y, Z, T of the V entries
+constexpr int JT_YEXT = JT_VEXT + JT_VA_ENTRIES * PTC_WORDS;   // X, Y, Z, T of Y and 2Y
+constexpr int JT_HXY = JT_YEXT + 2 * PTC_WORDS;                // affine x, y of H
+constexpr int JT_GXY = JT_HXY + 2 * NL;                        // affine x, y of Gamma
+constexpr int JT_VPFX = JT_GXY + 2 * NL;                       // slot 0: P = Z_1 ... Z_7; slot u: Z_1 ... Z_(u-1)
+constexpr int JT_V = JT_VA;                                    // VA = false: the 15 cached entries ...
+constexpr int JT_EXT = JT_VPFX;                                // ... and X, Y, Z, T of entries 1..8 (8 is written, not read)
+static_assert(JT_VA >= JT_Y + JT_Y_ENTRIES * PTC_WORDS && JT_VA % 32 == 0 && PTA_WORDS <= JT_VA_STRIDE &&
+              (VERIFY_TABS * WIN_TABLE_WORDS) % 32 == 0, "a V entry is one 128-byte line of a 128-byte aligned region");
+static_assert(3 * PTC_WORDS <= (JT_VA_ENTRIES - 1) * JT_VA_STRIDE, "the cached bases are parked behind entry 0 of JT_VA");
+static_assert(JT_VPFX + JT_VA_ENTRIES * NL <= VERIFY_TABS * WIN_TABLE_WORDS, "the joint tables and their parking fit the item's region");
+static_assert(JT_V + JT_V_ENTRIES * PTC_WORDS <= JT_YEXT && JT_EXT >= JT_GXY + 2 * NL && JT_EXT + 8 * PTC_WORDS <= VERIFY_TABS * WIN_TABLE_WORDS,
+              "the cached form of V's table keeps clear of JT_Y, JT_YEXT and the parked points");
 
 VRF_HD void pte_store(uint32_t* m, const PtE& p) {
   fe_store(m, p.X); fe_store(m + NL, p.Y); fe_store(m + 2 * NL, p.Z); fe_store(m + 3 * NL, p.T);
@@ -930,6 +967,63 @@ VRF_HD void build_joint_v_table(uint32_t* reg, const uint32_t c[8], const uint32
   }
 }
 
+// The 8 entries of JT_VA in extended coordinates (JT_VEXT) from the parked affine H and Gamma and the proof's scalars (c, s as
+// load_cs_reduced leaves them -- exactly what the V ladder decomposes again).  Q0 is entry 0, affine as it stands: it goes
+// straight to JT_VA.  Q1, Q2, Q3 wait as cached operands behind it, where the other affine entries go later; then entry
+// u = entry (u - 2^hb) + Q_(1 + hb), hb the highest set bit of u: 7 additions, one call site.  Leaves the products of the
+// entries' Z coordinates in JT_VPFX for joint_va_normalise.
+template <class S>
+VRF_HD void build_joint_va_table(uint32_t* reg, const uint32_t c[8], const uint32_t s[8]) {
+  GlvHalf h[4];
+  glv_decompose_bs(h[0], h[1], c);
+  glv_decompose_bs(h[2], h[3], s);
+  const bool neg0 = !h[0].neg, neg1 = !h[1].neg, neg2 = h[2].neg, neg3 = h[3].neg;       // the c terms are subtracted
+#pragma unroll 1
+  for (int p = 0; p < 2; ++p) {                 // p = 0: Gamma -> Q0, Q1; p = 1: H -> Q2, Q3
+    const uint32_t* xy = reg + (p == 0 ? JT_GXY : JT_HXY);
+    const bool nb = p == 0 ? neg0 : neg2, npsi = p == 0 ? neg1 : neg3;
+    const FeN x = fe_mul(fe_cneg(nb, fe_load<1, 4>(xy)), fe_one());       // -x as a product: back to a storage bound
+    const PtE b = te_from_affine(x, fe_load<1, 2>(xy + NL));
+    const PtE q = te_psi_signed<S>(b, nb != npsi);
+    const PtC bc = te_to_cached<S>(b);
+    if (p == 0) {
+      PtA a;
+      a.x = x; a.y = fe_load<1, 2>(xy + NL); a.dt = bc.dT;
+      pta_store(reg + JT_VA, a);
+      pte_store(reg + JT_VEXT, b);
+    } else {
+      ptc_store(reg + JT_VA + JT_VA_STRIDE + PTC_WORDS, bc);
+    }
+    ptc_store(reg + JT_VA + JT_VA_STRIDE + 2 * p * PTC_WORDS, te_to_cached<S>(q));
+  }
+  FeN run = fe_one();
+#pragma unroll 1
+  for (int u = 1; u < JT_VA_ENTRIES; ++u) {
+    const int hb = u >= 4 ? 2 : (u >= 2 ? 1 : 0);
+    const PtE e = te_add_cached<S>(pte_load(reg + JT_VEXT + (u - (1 << hb)) * PTC_WORDS),
+                                   ptc_load(reg + JT_VA + JT_VA_STRIDE + hb * PTC_WORDS), false);
+    pte_store(reg + JT_VEXT + u * PTC_WORDS, e);
+    fe_store(reg + JT_VPFX + u * NL, run);
+    run = fe_mul(run, e.Z);
+  }
+  fe_store(reg + JT_VPFX, run);
+}
+// JT_VA from JT_VEXT, given pinv = 1 / P (build_joint_va_table left P in slot 0 of JT_VPFX): the usual walk back through the
+// prefix products gives each 1 / Z; x = X / Z, y = Y / Z, d x y = d T / Z.  pinv = 0 (P = 0: possible only for points off
+// the prime-order subgroup, which the pre-validated flags let through) leaves entries of zeros.
+template <class S>
+VRF_HD void joint_va_normalise(uint32_t* reg, FeN inv) {
+#pragma unroll 1
+  for (int u = JT_VA_ENTRIES - 1; u >= 1; --u) {
+    const PtE e = pte_load(reg + JT_VEXT + u * PTC_WORDS);
+    const FeN zi = fe_mul(inv, fe_load<1, 2>(reg + JT_VPFX + u * NL));
+    inv = fe_mul(inv, e.Z);
+    PtA a;
+    a.x = fe_mul(e.X, zi); a.y = fe_mul(e.Y, zi); a.dt = fe_mul(fe_mul(e.T, zi), S::d());
+    pta_store(reg + JT_VA + u * JT_VA_STRIDE, a);
+  }
+}
+
 // tabs: 6 * WIN_TABLE_WORDS words (GLV table pairs of Y, H, Gamma).  Returns validity.
 template <class S>
 VRF_HD bool verify_decode_item(const DevTables& T, const uint32_t pk[8], const uint32_t hh[8],
@@ -969,11 +1063,13 @@ constexpr int DEC_SLOT = 4 * NL;
 // NP = 3: pk, H, Gamma (table slots 0, 1, 2); NP = 2 (keyed verification: the key's tables are context
 // resident): H, Gamma (pk is not read, slots 1, 2); NP = 2 with SKIP_H (verification from alpha: H came out of
 // hash-to-curve in this call and its tables are already in slot 1): pk, Gamma (slots 0, 2).
-// JOINT (the GLV suite's IETF verifier): the item's region gets the joint tables instead -- JT_Y from pk, JT_V once H and
+// JOINT (the GLV suite's IETF verifier): the item's region gets the joint tables instead -- JT_Y from pk, JT_VA once H and
 // Gamma of the item are both parked (the loop below meets Gamma first; with SKIP_H, H's affine x, y are already there), from
-// the proof's scalars in c_arr, s_arr.
+// the proof's scalars in c_arr, s_arr.  JT_VA is built in extended coordinates and made affine by one inversion: where a pk
+// is decoded it comes last, and the inversion rides on its inverse root (decode_by_inv_root_ride); the keyed form calls fe_inv.
+// VA = false: JT_V, the cached form of V's table, in its place (no ride, no inversion).
 // One pass: each point is decoded, decompressed, turned into its tables (or parked) and tested for the subgroup.
-template <class S, int NP = 3, bool SKIP_H = false, bool JOINT = false>
+template <class S, int NP = 3, bool SKIP_H = false, bool JOINT = false, bool VA = false>
 VRF_HD void verify_decode_multi(int K, const DevTables& T, size_t first, size_t n, const uint8_t* pk,
                                 const uint8_t* hh, const uint8_t* gamma, uint32_t* tabs_base,
                                 uint32_t* scratch_base, uint8_t* flags, uint32_t check_mask = 0,
@@ -992,9 +1088,17 @@ VRF_HD void verify_decode_multi(int K, const DevTables& T, size_t first, size_t 
       for (int k = 0; k < 8; ++k) enc[k] = w[k];
       const DecodeA a = decode_phase_a<S>(enc);
       Fe<1, 4> x;
-      bool ok = decode_by_inv_root<S>(x, a, T.sq);
+      bool ok;
       if constexpr (JOINT) {
+        // pk comes last and the item's V entries are there by then: their common inverse rides on pk's root.  The keyed
+        // form decodes no pk and inverts on its own.
+        constexpr bool RIDE = VA && (NP == 3 || SKIP_H);
         uint32_t* reg = tabs_base + item * (VERIFY_TABS * WIN_TABLE_WORDS);
+        const bool ride = RIDE && p == 0;
+        FeN P = fe_one(), pinv = fe_zero();
+        if (ride) P = fe_load<1, 2>(reg + JT_VPFX);
+        ok = decode_by_inv_root_ride<S>(x, pinv, ride, P, a, T.sq);
+        if (ride) joint_va_normalise<S>(reg, pinv);
         if (p == 0) build_joint_y_table<S>(reg, x, a.y);
         else jt_park_xy(reg + (p == 1 ? JT_HXY : JT_GXY), x, a.y);
         if (p == (SKIP_H ? 2 : 1)) {
@@ -1004,9 +1108,15 @@ VRF_HD void verify_decode_multi(int K, const DevTables& T, size_t first, size_t 
 #pragma unroll
           for (int k = 0; k < 8; ++k) { c[k] = wc[k]; s[k] = ws[k]; }
           load_cs_reduced<S>(c, s);
-          build_joint_v_table<S>(reg, c, s);
+          if constexpr (VA) {
+            build_joint_va_table<S>(reg, c, s);
+            if constexpr (!RIDE) joint_va_normalise<S>(reg, fe_inv(fe_load<1, 2>(reg + JT_VPFX)));
+          } else {
+            build_joint_v_table<S>(reg, c, s);
+          }
         }
       } else {
+        ok = decode_by_inv_root<S>(x, a, T.sq);
         uint32_t* tab = tabs_base + item * (VERIFY_TABS * WIN_TABLE_WORDS) + p * 2 * WIN_TABLE_WORDS;
         build_glv_tables<S>(tab, x, a.y);
       }
@@ -1096,8 +1206,8 @@ VRF_HD void verify_finish_multi(int K, size_t first, size_t n, uint32_t* pts_bas
 // Same stage for callers that hold affine points in memory (arkworks `Affine { x, y }`): x || y as
 // 32-byte little-endian canonical integers, no square roots.  Validity = coordinates < q and the
 // point is on the curve.
-// JOINT: as in verify_decode_multi; c, s as load_cs_reduced leaves them.
-template <class S, bool JOINT = false>
+// JOINT, VA: as in verify_decode_multi; c, s as load_cs_reduced leaves them.
+template <class S, bool JOINT = false, bool VA = false>
 VRF_HD bool verify_decode_affine_item(uint32_t enc_out[3][8], const uint32_t (&xy)[3][16], uint32_t* tabs,
                                       const SqrtTables& T, uint32_t check_mask = 0, bool mont256 = false,
                                       const uint32_t* c = nullptr, const uint32_t* s = nullptr) {
@@ -1134,7 +1244,12 @@ VRF_HD bool verify_decode_affine_item(uint32_t enc_out[3][8], const uint32_t (&x
       if (p == 2) enc_out[2][j] = e[j];
     }
   }
-  if constexpr (JOINT) build_joint_v_table<S>(tabs, c, s);
+  if constexpr (JOINT && VA) {      // no root to ride on: the V entries' common inverse is an inversion of its own
+    build_joint_va_table<S>(tabs, c, s);
+    joint_va_normalise<S>(tabs, fe_inv(fe_load<1, 2>(tabs + JT_VPFX)));
+  } else if constexpr (JOINT) {
+    build_joint_v_table<S>(tabs, c, s);
+  }
   return valid;
 }
 
@@ -1196,13 +1311,16 @@ VRF_HD void verify_straus_item(uint32_t* out_uv, const DevTables& T, const uint3
   }
 }
 
-// The same two results from the joint tables (GLV suite; build_joint_y_table / build_joint_v_table above).
+// The same two results from the joint tables (GLV suite; build_joint_y_table / build_joint_va_table above).
 // HALF 0: -c*Y by 64 windows of two doublings and one addition: signed radix-4 digits of the two halves, each with its half's
 //         sign (negated: the term is subtracted), the pair normalised to a JT_Y entry and one negation flag; then s*G from
 //         the fixed-base table, so the last addition keeps T.
-// HALF 1: V bit by bit, 126..0: one doubling (with T: an addition follows) and one addition (without: a doubling follows, or
-//         nothing reads it) of the JT_V entry the four magnitudes' bits select; entry 0 is the neutral element.  The first
-//         bit is a plain load.  Bit 127 of a half is never set (fr.cuh GLV_HALF_TOP_WORD_CAP).
+// HALF 1: V digit by digit, 127..0, over the sign-aligned recoding of the four magnitudes (fr.cuh glv_recode_sac; 128 digits
+//         because bit 127 of a half is never set, GLV_HALF_TOP_WORD_CAP): one doubling (with T: an addition follows) and one
+//         mixed addition or subtraction (without T: a doubling follows; the last keeps it for the correction) of the affine
+//         JT_VA entry the digit selects -- no entry is neutral, every digit adds.  The first digit is a plain load.  Where half 0
+//         is even the walk ran with half 0 + 1 and Q0 (entry 0) is subtracted at the end, through a select.
+//         VA = false walks the cached form of the table (JT_V) bit by bit, as before: the host simulation's second implementation.
 template <class S>
 VRF_HD PtE joint_u_ladder(const uint32_t* ytab, const GlvHalf& c1, const GlvHalf& c2) {
   uint32_t r1[4], r2[4];
@@ -1227,6 +1345,7 @@ VRF_HD int joint_v_index(const uint32_t (&m)[4][4], int bit) {
   return scalar_bit_128(m[0], bit) | (scalar_bit_128(m[1], bit) << 1) | (scalar_bit_128(m[2], bit) << 2) |
          (scalar_bit_128(m[3], bit) << 3);
 }
+// VA = false: bits 126..0 of the four magnitudes select one of the 15 cached entries of JT_V, entry 0 the neutral element
 template <class S>
 VRF_HD PtE joint_v_ladder(const uint32_t* vtab, const uint32_t (&m)[4][4]) {
   const PtC first = win_lookup(vtab, joint_v_index(m, 126));
@@ -1239,7 +1358,24 @@ VRF_HD PtE joint_v_ladder(const uint32_t* vtab, const uint32_t (&m)[4][4]) {
   }
   return acc;
 }
-template <class S, int HALF>
+template <class S>
+VRF_HD PtE joint_va_ladder(const uint32_t* vtab, const uint32_t (&m)[4][4]) {
+  SacV r;
+  glv_recode_sac(r, m);
+  const PtA first = pta_load(vtab + sac_index(r, 127) * JT_VA_STRIDE);        // digit 127 is +1
+  PtE acc;
+  acc.X = first.x; acc.Y = first.y; acc.Z = fe_one(); acc.T = fe_zero();
+#pragma unroll 1
+  for (int bit = 126; bit >= 0; --bit) {
+    acc = te_dbl<S, true>(acc, true);
+    acc = te_add_affine<S, true>(acc, pta_load(vtab + sac_index(r, bit) * JT_VA_STRIDE), sac_neg(r, bit), bit == 0);
+  }
+  // the walk ran with half 0 + 1 where half 0 is even: take Q0 back, every lane in the same shape
+  const PtE fixed = te_add_affine<S, true>(acc, pta_load(vtab), true, false);
+  acc.X = fe_select(r.fix, fixed.X, acc.X); acc.Y = fe_select(r.fix, fixed.Y, acc.Y); acc.Z = fe_select(r.fix, fixed.Z, acc.Z);
+  return acc;
+}
+template <class S, int HALF, bool VA = false>
 VRF_HD void verify_joint_item(uint32_t* out_uv, const DevTables& T, const uint32_t* reg, const uint32_t c[8],
                               const uint32_t s[8]) {
   GlvHalf h[4];
@@ -1255,7 +1391,8 @@ VRF_HD void verify_joint_item(uint32_t* out_uv, const DevTables& T, const uint32
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int i = 0; i < 4; ++i) m[t][i] = h[t].mag[i];
-    r = joint_v_ladder<S>(reg + JT_V, m);
+    if constexpr (VA) r = joint_va_ladder<S>(reg + JT_VA, m);
+    else r = joint_v_ladder<S>(reg + JT_V, m);
   }
   fe_store(out_uv, r.X);
   fe_store(out_uv + NL, r.Y);
