@@ -5,7 +5,7 @@ Host-side mirror (Python) of the Rust surface re-exported at /root/reference src
 over the C ABI of ``csrc/libvrfhip.so``.  All arithmetic runs in hand-written HIP kernels.
 """
 from .api import (  # noqa: F401
-    KeySet, G1Srs, SuiteDesc, PinnedBuffer, ietf_verify_batch_multi, ietf_prove_batch_multi, pedersen_prove_batch_multi,
+    KeySet, G1Srs, FrDomain, NTT_INVERSE, SuiteDesc, PinnedBuffer, ietf_verify_batch_multi, ietf_prove_batch_multi, pedersen_prove_batch_multi,
     pedersen_verify_batch_multi, ietf_verify_batch_affine_multi, pedersen_verify_batch_affine_multi, CURVE_BANDERSNATCH, CURVE_JUBJUB, CURVE_ED25519, CURVE_BABY_JUBJUB, CURVE_SECP256R1, CURVE_BANDERSNATCH_SW,
     BandersnatchSha512Ell2, JubJubSha512Tai, Ed25519Sha512Tai, BabyJubJubSha512Tai, Secp256r1Sha256Tai, BandersnatchSwSha512Tai, Context, Error, IetfProof, Input, Output, Public, Secret, Suite,
     VerificationFailure, InvalidData, ietf, pedersen, PedersenProof, default_context,

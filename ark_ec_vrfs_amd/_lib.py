@@ -40,6 +40,10 @@ SYMBOLS = [
     "vrfhip_g1_srs_create", "vrfhip_g1_srs_destroy", "vrfhip_g1_srs_size", "vrfhip_g1_srs_bytes",
     "vrfhip_kzg_commit_batch", "vrfhip_kzg_commit_batch_dev", "vrfhip_kzg_open_batch", "vrfhip_kzg_open_batch_dev",
     "vrfhip_test_g1_msm_groups",
+    "vrfhip_fr_domain_create", "vrfhip_fr_domain_destroy", "vrfhip_fr_domain_size", "vrfhip_fr_domain_bytes",
+    "vrfhip_test_fr_ntt_passes", "vrfhip_fr_ntt_batch", "vrfhip_fr_ntt_batch_dev",
+    "vrfhip_kzg_commit_evals_batch", "vrfhip_kzg_commit_evals_batch_dev",
+    "vrfhip_kzg_open_evals_batch", "vrfhip_kzg_open_evals_batch_dev",
     "vrfhip_kzg_multi_check_batch", "vrfhip_kzg_multi_check_batch_dev", "vrfhip_kzg_multi_check_batch_rlc",
     "vrfhip_kzg_multi_check_batch_rlc_dev",
     "vrfhip_hash_to_curve_batch", "vrfhip_hash_to_curve_batch_dev",
@@ -199,6 +203,18 @@ def load() -> ctypes.CDLL:
     lib.vrfhip_kzg_open_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, P, P, P, P, P, P]
     lib.vrfhip_kzg_open_batch_dev.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, P, P, P, P, P, P, c_void_p]
     lib.vrfhip_test_g1_msm_groups.argtypes = [c_void_p, c_size_t, c_int32, c_int32]
+    lib.vrfhip_fr_domain_create.argtypes = [c_void_p, c_uint32, P, POINTER(c_void_p)]
+    lib.vrfhip_fr_domain_destroy.argtypes = [c_void_p]
+    lib.vrfhip_fr_domain_destroy.restype = None
+    lib.vrfhip_fr_domain_size.argtypes = lib.vrfhip_fr_domain_bytes.argtypes = [c_void_p]
+    lib.vrfhip_fr_domain_size.restype = lib.vrfhip_fr_domain_bytes.restype = c_size_t
+    lib.vrfhip_test_fr_ntt_passes.argtypes = [c_void_p, c_uint32]
+    lib.vrfhip_fr_ntt_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_uint32, P, P, P]
+    lib.vrfhip_fr_ntt_batch_dev.argtypes = [c_void_p, c_void_p, c_size_t, c_uint32, P, P, P, c_void_p]
+    lib.vrfhip_kzg_commit_evals_batch.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, P, P, P, P]
+    lib.vrfhip_kzg_commit_evals_batch_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, P, P, P, P, c_void_p]
+    lib.vrfhip_kzg_open_evals_batch.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, P, P, P, P, P, P]
+    lib.vrfhip_kzg_open_evals_batch_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, P, P, P, P, P, P, c_void_p]
     kzgm = [c_void_p, c_size_t, c_uint32, c_uint32, c_uint32] + [P] * 8    # ctx, n, (k, m, p), the seven arrays, vk
     lib.vrfhip_kzg_multi_check_batch.argtypes = kzgm + [P]
     lib.vrfhip_kzg_multi_check_batch_dev.argtypes = kzgm + [P, c_void_p]
@@ -240,7 +256,8 @@ def load() -> ctypes.CDLL:
         fn = getattr(lib, name)
         if name not in ("vrfhip_last_error", "vrfhip_ctx_destroy", "vrfhip_ctx_workspace_bytes", "vrfhip_host_free",
                         "vrfhip_keyset_destroy", "vrfhip_keyset_bytes", "vrfhip_g1_srs_destroy", "vrfhip_g1_srs_size",
-                        "vrfhip_g1_srs_bytes", "vrfhip_ctx_get_flags", "vrfhip_ctx_point_bytes",
+                        "vrfhip_g1_srs_bytes", "vrfhip_fr_domain_destroy", "vrfhip_fr_domain_size", "vrfhip_fr_domain_bytes",
+                        "vrfhip_ctx_get_flags", "vrfhip_ctx_point_bytes",
                         "vrfhip_ctx_hash_bytes"):
             fn.restype = c_int32
     _lib = lib

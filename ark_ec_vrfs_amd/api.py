@@ -177,6 +177,9 @@ class PinnedBuffer:
             pass
 
 
+NTT_INVERSE = 1       # VRFHIP_NTT_INVERSE
+
+
 def _np_u8(b, n_bytes: Optional[int] = None) -> np.ndarray:
     a = np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray) else b
     a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
@@ -837,6 +840,86 @@ class Context:
                                                        None if proof_xy is None else proof_xy.data_ptr(), status.data_ptr(), st),
                    "vrfhip_kzg_open_batch_dev")
 
+    # ---- radix-2 transforms over Fr; commitments and openings from evaluations ---------------
+    def fr_domain_create(self, log_n: int, offset=None) -> "FrDomain":
+        """`Radix2EvaluationDomain` of size 2^log_n (log_n <= 20) kept in HBM: element i is offset * w^i.  offset: None = the
+        plain domain, else a scalar (an integer, or 32 bytes little-endian) 0 < offset < r = `get_coset(offset)`."""
+        off = None
+        if offset is not None:
+            off = np.frombuffer(int(offset).to_bytes(32, "little"), np.uint8) if isinstance(offset, int) else _np_u8(offset, 32)
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.vrfhip_fr_domain_create(self._h, log_n, None if off is None else _ptr(off), ctypes.byref(h)),
+                   "vrfhip_fr_domain_create")
+        return FrDomain(self, h, log_n)
+
+    def fr_ntt_passes(self, log_n: int) -> int:
+        """Test hook: the kernel launches one transform of size 2^log_n runs on this device."""
+        rc = self._lib.vrfhip_test_fr_ntt_passes(self._h, log_n)
+        if rc <= 0:
+            _lib.check(rc if rc else -1, "vrfhip_test_fr_ntt_passes")
+        return rc
+
+    def fr_ntt_batch(self, dom, cols, inverse: bool = False):
+        """`fft` / `coset_fft` (inverse: `ifft` / `coset_ifft`) of k columns at once: cols (k, n, 32) little-endian < r,
+        natural order -> (out (k, n, 32), status (k,)); status 2 and a zero column where a scalar is >= r."""
+        c = np.ascontiguousarray(cols, dtype=np.uint8)
+        if c.ndim != 3 or c.shape[2] != 32 or c.shape[1] != dom.n:
+            raise ValueError("cols must have shape (k, n, 32) with n the size of the domain")
+        out, st = np.empty_like(c), np.empty(c.shape[0], np.uint8)
+        _lib.check(self._lib.vrfhip_fr_ntt_batch(self._h, dom.handle, c.shape[0], NTT_INVERSE if inverse else 0, _ptr(c),
+                                                 _ptr(out), _ptr(st)), "vrfhip_fr_ntt_batch")
+        return out, st
+
+    def fr_ntt_batch_dev(self, dom, cols, out, status, inverse: bool = False, stream=None, flags=None):
+        """Device form: tensors cols / out (k, n, 32) (the same tensor transforms in place), status (k,)."""
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        fl = (NTT_INVERSE if inverse else 0) if flags is None else flags
+        _lib.check(self._lib.vrfhip_fr_ntt_batch_dev(self._h, dom.handle, cols.shape[0], fl, cols.data_ptr(), out.data_ptr(),
+                                                     status.data_ptr(), st), "vrfhip_fr_ntt_batch_dev")
+
+    def kzg_commit_evals_batch(self, srs, dom, evals):
+        """kzg_commit_batch of the polynomials with these values over `dom`: evals (k, n, 32) ->
+        (out48 (k, 48), out_xy (k, 96), status (k,)); the interpolation runs on the device."""
+        c = np.ascontiguousarray(evals, dtype=np.uint8)
+        if c.ndim != 3 or c.shape[2] != 32 or c.shape[1] != dom.n:
+            raise ValueError("evals must have shape (k, n, 32) with n the size of the domain")
+        k = c.shape[0]
+        out, xy, st = np.empty((k, 48), np.uint8), np.empty((k, 96), np.uint8), np.empty(k, np.uint8)
+        _lib.check(self._lib.vrfhip_kzg_commit_evals_batch(self._h, srs.handle, dom.handle, k, _ptr(c), _ptr(out), _ptr(xy),
+                                                           _ptr(st)), "vrfhip_kzg_commit_evals_batch")
+        return out, xy, st
+
+    def kzg_commit_evals_batch_dev(self, srs, dom, evals, out48, status, out_xy=None, stream=None):
+        """Device form: tensors evals (k, n, 32), out48 (k, 48), status (k,), out_xy (k, 96) optional."""
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _lib.check(self._lib.vrfhip_kzg_commit_evals_batch_dev(self._h, srs.handle, dom.handle, evals.shape[0], evals.data_ptr(),
+                                                               out48.data_ptr(), None if out_xy is None else out_xy.data_ptr(),
+                                                               status.data_ptr(), st), "vrfhip_kzg_commit_evals_batch_dev")
+
+    def kzg_open_evals_batch(self, srs, dom, evals, points):
+        """kzg_open_batch of the polynomials with these values over `dom`: evals (k, n, 32), points (k, 32) ->
+        (value (k, 32), proof48 (k, 48), proof_xy (k, 96), status (k,))."""
+        c = np.ascontiguousarray(evals, dtype=np.uint8)
+        z = np.ascontiguousarray(points, dtype=np.uint8).reshape(-1, 32)
+        if c.ndim != 3 or c.shape[2] != 32 or c.shape[1] != dom.n or z.shape[0] != c.shape[0]:
+            raise ValueError("evals must have shape (k, n, 32) with n the size of the domain and points (k, 32)")
+        k = c.shape[0]
+        v, out, xy, st = np.empty((k, 32), np.uint8), np.empty((k, 48), np.uint8), np.empty((k, 96), np.uint8), np.empty(k, np.uint8)
+        _lib.check(self._lib.vrfhip_kzg_open_evals_batch(self._h, srs.handle, dom.handle, k, _ptr(c), _ptr(z), _ptr(v), _ptr(out),
+                                                         _ptr(xy), _ptr(st)), "vrfhip_kzg_open_evals_batch")
+        return v, out, xy, st
+
+    def kzg_open_evals_batch_dev(self, srs, dom, evals, points, value, proof48, status, proof_xy=None, stream=None):
+        """Device form: tensors evals (k, n, 32), points / value (k, 32), proof48 (k, 48), status (k,), proof_xy optional."""
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        _lib.check(self._lib.vrfhip_kzg_open_evals_batch_dev(self._h, srs.handle, dom.handle, evals.shape[0], evals.data_ptr(),
+                                                             points.data_ptr(), value.data_ptr(), proof48.data_ptr(),
+                                                             None if proof_xy is None else proof_xy.data_ptr(),
+                                                             status.data_ptr(), st), "vrfhip_kzg_open_evals_batch_dev")
+
     @staticmethod
     def _kzg_multi_shape(n, commitments, scalars, shared_bases, shared_scalars, proofs, points, coefs):
         """(k, m, p) from the arrays' second dimensions -- arrays or tensors of shape (n, count, width), None = count 0 --
@@ -1223,6 +1306,24 @@ class G1Srs:
     def close(self) -> None:
         if self.handle:
             self._ctx._lib.vrfhip_g1_srs_destroy(self.handle)
+            self.handle = None
+
+
+class FrDomain:
+    """Device-resident radix-2 evaluation domain of Fr (vrfhip_fr_domain); destroy before its Context."""
+
+    def __init__(self, ctx: Context, handle, log_n: int):
+        self._ctx, self.handle, self.log_n, self.n = ctx, handle, log_n, 1 << log_n
+
+    def size(self) -> int:
+        return int(self._ctx._lib.vrfhip_fr_domain_size(self.handle))
+
+    def bytes(self) -> int:
+        return int(self._ctx._lib.vrfhip_fr_domain_bytes(self.handle))
+
+    def close(self) -> None:
+        if self.handle:
+            self._ctx._lib.vrfhip_fr_domain_destroy(self.handle)
             self.handle = None
 
 

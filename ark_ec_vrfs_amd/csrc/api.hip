@@ -180,6 +180,14 @@ struct vrfhip_g1_srs {
   size_t bytes = 0;
 };
 
+// a radix-2 evaluation domain of Fr resident in HBM (transforms; commitments and openings from evaluations)
+struct vrfhip_fr_domain {
+  vrfhip_ctx* ctx = nullptr;
+  FrNttTables T{};                // msm_g1.h: w, off, offi, consts carved from d_mem
+  uint32_t* d_mem = nullptr;
+  size_t bytes = 0;
+};
+
 namespace {
 
 struct DeviceGuard {
@@ -2481,6 +2489,274 @@ int32_t vrfhip_kzg_open_batch(vrfhip_ctx* ctx, const void* handle, size_t k, siz
   HIP_TRY(hipMemcpyAsync(d_z, z, k * 32, hipMemcpyHostToDevice, ctx->stream));
   rc = vrfhip_kzg_open_batch_dev(ctx, srs, k, len, d_c, d_z, d_v, d_o, proof_xy ? d_xy : nullptr, d_st, ctx->stream);
   HIP_TRY(hipMemsetAsync(d_c, 0, k * len * 32, ctx->stream));                      // staged coefficients
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(value, d_v, k * 32, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(proof48, d_o, k * 48, hipMemcpyDeviceToHost, ctx->stream));
+  if (proof_xy) HIP_TRY(hipMemcpyAsync(proof_xy, d_xy, k * 96, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(status, d_st, k, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+
+// ------------------------------------------------------------------------- radix-2 transforms over Fr (k_fr_ntt.hip)
+int32_t vrfhip_fr_domain_create(vrfhip_ctx* ctx, uint32_t log_n, const uint8_t* offset32, void** out) {
+  if (!out) return fail(VRFHIP_ERR_BAD_ARG, "out is NULL");
+  *out = nullptr;
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
+  if (log_n > (uint32_t)fr_ntt_max_log()) return fail(VRFHIP_ERR_BAD_ARG, "log_n too large (at most 20)");
+  if (offset32) {
+    uint32_t w[8], any = 0;
+    std::memcpy(w, offset32, 32);
+    bool lt = false;
+    for (int j = 7; j >= 0; --j)
+      if (w[j] != vrfk::Q32[j]) { lt = w[j] < vrfk::Q32[j]; break; }
+    for (int j = 0; j < 8; ++j) any |= w[j];
+    if (!lt || !any) return fail(VRFHIP_ERR_BAD_ARG, "the offset of a coset must be nonzero and below r");
+  }
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  std::unique_ptr<vrfhip_fr_domain, void (*)(void*)> owner(new vrfhip_fr_domain(), vrfhip_fr_domain_destroy);
+  vrfhip_fr_domain* dom = owner.get();
+  dom->ctx = ctx;
+  const size_t tw = fr_ntt_table_words(log_n), cw = fr_ntt_const_words();
+  dom->bytes = ((offset32 ? 3 : 1) * tw + cw) * sizeof(uint32_t);
+  HIP_TRY(hipMalloc(&dom->d_mem, dom->bytes + 32));                    // + the staged offset
+  dom->T.log_n = log_n;
+  dom->T.consts = dom->d_mem;
+  dom->T.w = dom->d_mem + cw;
+  dom->T.off = offset32 ? dom->T.w + tw : nullptr;
+  dom->T.offi = offset32 ? dom->T.off + tw : nullptr;
+  uint8_t* d_offset = reinterpret_cast<uint8_t*>(dom->d_mem) + dom->bytes;
+  if (offset32) HIP_TRY(hipMemcpyAsync(d_offset, offset32, 32, hipMemcpyHostToDevice, ctx->stream));
+  launch_fr_domain_fill(dom->T, offset32 ? d_offset : nullptr, ctx->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  *out = owner.release();
+  return VRFHIP_SUCCESS;
+}
+
+void vrfhip_fr_domain_destroy(void* handle) {
+  vrfhip_fr_domain* dom = static_cast<vrfhip_fr_domain*>(handle);
+  if (!dom) return;
+  if (dom->ctx && dom->d_mem) {
+    DeviceGuard guard(dom->ctx->device);
+    (void)hipFree(dom->d_mem);
+  }
+  delete dom;
+}
+size_t vrfhip_fr_domain_size(const void* dom) {
+  return dom ? size_t(1) << static_cast<const vrfhip_fr_domain*>(dom)->T.log_n : 0;
+}
+size_t vrfhip_fr_domain_bytes(const void* dom) { return dom ? static_cast<const vrfhip_fr_domain*>(dom)->bytes : 0; }
+int32_t vrfhip_test_fr_ntt_passes(vrfhip_ctx* ctx, uint32_t log_n) {
+  if (!ctx || log_n > (uint32_t)fr_ntt_max_log()) return fail(VRFHIP_ERR_BAD_ARG, "NULL ctx or log_n above 20");
+  return fr_ntt_passes(log_n);
+}
+}  // extern "C"
+
+namespace {
+constexpr size_t NTT_GROUP_SCALARS = size_t(1) << 21;         // scalars of one launch group of a transform (64 MiB staged)
+int32_t fr_ntt_args(vrfhip_ctx* ctx, const vrfhip_fr_domain* dom, size_t k) {
+  if (!ctx) return fail(VRFHIP_ERR_BAD_ARG, "ctx is NULL");
+  if (ctx->sw) return fail(VRFHIP_ERR_UNSUPPORTED, P256_UNSUPPORTED_MSG);
+  if (!dom || dom->ctx != ctx) return fail(VRFHIP_ERR_BAD_ARG, "domain is NULL or of another context");
+  if (k == 0) return fail(VRFHIP_ERR_BAD_ARG, "k must be at least 1");
+  if (k > (size_t(1) << 28)) return fail(VRFHIP_ERR_BAD_ARG, "batch too large");
+  return VRFHIP_SUCCESS;
+}
+// The inverse transforms of `m` columns of evaluations into the coefficient region at the head of the MSM workspace, for the
+// launch group that follows: coefficients (m n 32 B) | the transform's scratch (as much again, plans of several passes) |
+// its statuses | the group's layout.  *layout_off: where that layout begins.
+struct EvalsRegion {
+  uint8_t *coeffs, *scratch, *ntt_status;
+  size_t layout_off, secret_bytes;
+};
+EvalsRegion evals_region(vrfhip_ctx* ctx, const vrfhip_fr_domain* dom, size_t cols) {
+  EvalsRegion e;
+  const size_t col_bytes = (size_t(32) << dom->T.log_n) * cols;
+  const bool staged = fr_ntt_passes(dom->T.log_n) > 1;
+  uint8_t* p = static_cast<uint8_t*>(ctx->d_msm_ws);
+  e.coeffs = p;
+  e.scratch = p + Stage::pad(col_bytes);
+  e.secret_bytes = Stage::pad(col_bytes) + (staged ? Stage::pad(col_bytes) : 0);
+  e.ntt_status = p + e.secret_bytes;
+  e.layout_off = e.secret_bytes + Stage::pad(cols);
+  return e;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t vrfhip_fr_ntt_batch_dev(vrfhip_ctx* ctx, const void* handle, size_t k, uint32_t flags, const uint8_t* d_in,
+                                uint8_t* d_out, uint8_t* d_status, void* stream) {
+  const vrfhip_fr_domain* dom = static_cast<const vrfhip_fr_domain*>(handle);
+  int32_t rc = fr_ntt_args(ctx, dom, k);
+  if (rc) return rc;
+  if (flags & ~(uint32_t)VRFHIP_NTT_INVERSE) return fail(VRFHIP_ERR_BAD_ARG, "unknown flag bits");
+  if (!d_in || !d_out || !d_status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t n = size_t(1) << dom->T.log_n, col = n * 32;
+  const size_t cap = std::min(k, std::max<size_t>(1, NTT_GROUP_SCALARS / n));
+  const bool staged = fr_ntt_passes(dom->T.log_n) > 1;
+  if (staged && (rc = ensure_msm_workspace(ctx, cap * col))) return rc;
+  uint8_t* scratch = staged ? static_cast<uint8_t*>(ctx->d_msm_ws) : nullptr;
+  rc = for_chunks(k, cap, [&](size_t base, size_t m) -> int32_t {
+    launch_fr_ntt(dom->T, m, (flags & VRFHIP_NTT_INVERSE) != 0, d_in + base * col, d_out + base * col, scratch, d_status + base,
+                  st);
+    if (staged) HIP_TRY(hipMemsetAsync(scratch, 0, m * col, st));       // functions of the (secret) columns
+    return VRFHIP_SUCCESS;
+  });
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return VRFHIP_SUCCESS;
+}
+
+int32_t vrfhip_fr_ntt_batch(vrfhip_ctx* ctx, const void* handle, size_t k, uint32_t flags, const uint8_t* in, uint8_t* out,
+                            uint8_t* status) {
+  const vrfhip_fr_domain* dom = static_cast<const vrfhip_fr_domain*>(handle);
+  int32_t rc = fr_ntt_args(ctx, dom, k);
+  if (rc) return rc;
+  if (flags & ~(uint32_t)VRFHIP_NTT_INVERSE) return fail(VRFHIP_ERR_BAD_ARG, "unknown flag bits");
+  if (!in || !out || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  const size_t bytes = (size_t(32) << dom->T.log_n) * k;
+  uint8_t *d_c, *d_st;
+  rc = stage_layout(ctx, [&](Stage& sg) { d_c = sg.take(bytes); d_st = sg.take(k); });
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(d_c, in, bytes, hipMemcpyHostToDevice, ctx->stream));
+  rc = vrfhip_fr_ntt_batch_dev(ctx, dom, k, flags, d_c, d_c, d_st, ctx->stream);
+  if (!rc) {
+    HIP_TRY(hipMemcpyAsync(out, d_c, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(status, d_st, k, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIP_TRY(hipMemsetAsync(d_c, 0, bytes, ctx->stream));                    // staged columns
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return rc;
+}
+
+int32_t vrfhip_kzg_commit_evals_batch_dev(vrfhip_ctx* ctx, const void* srs_handle, const void* dom_handle, size_t k,
+                                          const uint8_t* d_evals, uint8_t* d_out48, uint8_t* d_out_xy, uint8_t* d_status,
+                                          void* stream) {
+  const vrfhip_g1_srs* srs = static_cast<const vrfhip_g1_srs*>(srs_handle);
+  const vrfhip_fr_domain* dom = static_cast<const vrfhip_fr_domain*>(dom_handle);
+  int32_t rc = kzg_prove_args(ctx, srs, k);
+  if (rc) return rc;
+  if ((rc = fr_ntt_args(ctx, dom, k))) return rc;
+  const size_t len = size_t(1) << dom->T.log_n;
+  if (len > srs->n) return fail(VRFHIP_ERR_BAD_ARG, "the domain is larger than the base set");
+  if (!d_evals || !d_out48 || !d_status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t cap = kzg_prove_group(k, len);
+  const int groups = g1_msm_groups(len, (int)cap, G1_W_FULL, ctx->cus);
+  rc = ensure_msm_workspace(ctx, evals_region(ctx, dom, cap).layout_off + g1_shared_workspace_bytes(len, (int)cap, groups, 0));
+  if (rc) return rc;
+  rc = for_chunks(k, cap, [&](size_t base, size_t m) -> int32_t {
+    const EvalsRegion e = evals_region(ctx, dom, m);
+    launch_fr_ntt(dom->T, m, true, d_evals + base * len * 32, e.coeffs, e.scratch, e.ntt_status, st);
+    const int gr = g1_msm_groups(len, (int)m, G1_W_FULL, ctx->cus);
+    uint32_t* wg = nullptr;
+    const G1MsmLayout L = g1_shared_layout(len, (int)m, gr, 0, static_cast<uint8_t*>(ctx->d_msm_ws) + e.layout_off, srs->d_pts, &wg);
+    launch_kzg_commit(L, e.coeffs, d_out48 + base * 48, at(d_out_xy, base, 96), d_status + base, st, prof_events(ctx));
+    launch_fr_ntt_merge(m, e.ntt_status, d_out48 + base * 48, at(d_out_xy, base, 96), nullptr, d_status + base, st);
+    // the coefficients, and as in vrfhip_kzg_commit_batch_dev the digits, the sorted lists and the partial sums
+    HIP_TRY(hipMemsetAsync(e.coeffs, 0, e.secret_bytes, st));
+    HIP_TRY(hipMemsetAsync(L.digits, 0, g1_shared_secret_bytes(L), st));
+    return VRFHIP_SUCCESS;
+  });
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return VRFHIP_SUCCESS;
+}
+
+int32_t vrfhip_kzg_commit_evals_batch(vrfhip_ctx* ctx, const void* srs_handle, const void* dom_handle, size_t k,
+                                      const uint8_t* evals, uint8_t* out48, uint8_t* out_xy, uint8_t* status) {
+  const vrfhip_g1_srs* srs = static_cast<const vrfhip_g1_srs*>(srs_handle);
+  const vrfhip_fr_domain* dom = static_cast<const vrfhip_fr_domain*>(dom_handle);
+  int32_t rc = kzg_prove_args(ctx, srs, k);
+  if (rc) return rc;
+  if ((rc = fr_ntt_args(ctx, dom, k))) return rc;
+  if (!evals || !out48 || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  const size_t bytes = (size_t(32) << dom->T.log_n) * k;
+  uint8_t *d_c, *d_o, *d_xy, *d_st;
+  rc = stage_layout(ctx, [&](Stage& sg) { d_c = sg.take(bytes); d_o = sg.take(k * 48); d_xy = sg.take(k * 96); d_st = sg.take(k); });
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(d_c, evals, bytes, hipMemcpyHostToDevice, ctx->stream));
+  rc = vrfhip_kzg_commit_evals_batch_dev(ctx, srs, dom, k, d_c, d_o, out_xy ? d_xy : nullptr, d_st, ctx->stream);
+  HIP_TRY(hipMemsetAsync(d_c, 0, bytes, ctx->stream));                    // staged columns
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out48, d_o, k * 48, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_xy) HIP_TRY(hipMemcpyAsync(out_xy, d_xy, k * 96, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(status, d_st, k, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return VRFHIP_SUCCESS;
+}
+
+int32_t vrfhip_kzg_open_evals_batch_dev(vrfhip_ctx* ctx, const void* srs_handle, const void* dom_handle, size_t k,
+                                        const uint8_t* d_evals, const uint8_t* d_z, uint8_t* d_value, uint8_t* d_proof48,
+                                        uint8_t* d_proof_xy, uint8_t* d_status, void* stream) {
+  const vrfhip_g1_srs* srs = static_cast<const vrfhip_g1_srs*>(srs_handle);
+  const vrfhip_fr_domain* dom = static_cast<const vrfhip_fr_domain*>(dom_handle);
+  int32_t rc = kzg_prove_args(ctx, srs, k);
+  if (rc) return rc;
+  if ((rc = fr_ntt_args(ctx, dom, k))) return rc;
+  const size_t len = size_t(1) << dom->T.log_n;
+  if (len > srs->n) return fail(VRFHIP_ERR_BAD_ARG, "the domain is larger than the base set");
+  if (!d_evals || !d_z || !d_value || !d_proof48 || !d_status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t cap = kzg_prove_group(k, len), q_wgs = kzg_cut(len).wgs, pts_n = len - 1;
+  const int groups = g1_msm_groups(pts_n ? pts_n : 1, (int)cap, G1_W_FULL, ctx->cus);
+  rc = ensure_msm_workspace(ctx, evals_region(ctx, dom, cap).layout_off + g1_shared_workspace_bytes(pts_n, (int)cap, groups, q_wgs));
+  if (rc) return rc;
+  rc = for_chunks(k, cap, [&](size_t base, size_t m) -> int32_t {
+    const EvalsRegion e = evals_region(ctx, dom, m);
+    launch_fr_ntt(dom->T, m, true, d_evals + base * len * 32, e.coeffs, e.scratch, e.ntt_status, st);
+    const int gr = g1_msm_groups(pts_n ? pts_n : 1, (int)m, G1_W_FULL, ctx->cus);
+    uint32_t* wg = nullptr;
+    const G1MsmLayout L = g1_shared_layout(pts_n, (int)m, gr, q_wgs, static_cast<uint8_t*>(ctx->d_msm_ws) + e.layout_off, srs->d_pts, &wg);
+    launch_kzg_open(L, wg, e.coeffs, d_z + base * 32, d_value + base * 32, d_proof48 + base * 48, at(d_proof_xy, base, 96),
+                    d_status + base, st, prof_events(ctx));
+    launch_fr_ntt_merge(m, e.ntt_status, d_proof48 + base * 48, at(d_proof_xy, base, 96), d_value + base * 32, d_status + base, st);
+    HIP_TRY(hipMemsetAsync(e.coeffs, 0, e.secret_bytes, st));             // the coefficients
+    HIP_TRY(hipMemsetAsync(L.digits, 0, g1_shared_secret_bytes(L), st));  // as in vrfhip_kzg_open_batch_dev
+    return VRFHIP_SUCCESS;
+  });
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return VRFHIP_SUCCESS;
+}
+
+int32_t vrfhip_kzg_open_evals_batch(vrfhip_ctx* ctx, const void* srs_handle, const void* dom_handle, size_t k,
+                                    const uint8_t* evals, const uint8_t* z, uint8_t* value, uint8_t* proof48, uint8_t* proof_xy,
+                                    uint8_t* status) {
+  const vrfhip_g1_srs* srs = static_cast<const vrfhip_g1_srs*>(srs_handle);
+  const vrfhip_fr_domain* dom = static_cast<const vrfhip_fr_domain*>(dom_handle);
+  int32_t rc = kzg_prove_args(ctx, srs, k);
+  if (rc) return rc;
+  if ((rc = fr_ntt_args(ctx, dom, k))) return rc;
+  if (!evals || !z || !value || !proof48 || !status) return fail(VRFHIP_ERR_BAD_ARG, "NULL array");
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  DeviceGuard guard(ctx->device);
+  const size_t bytes = (size_t(32) << dom->T.log_n) * k;
+  uint8_t *d_c, *d_z, *d_v, *d_o, *d_xy, *d_st;
+  rc = stage_layout(ctx, [&](Stage& sg) {
+    d_c = sg.take(bytes); d_z = sg.take(k * 32); d_v = sg.take(k * 32);
+    d_o = sg.take(k * 48); d_xy = sg.take(k * 96); d_st = sg.take(k);
+  });
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(d_c, evals, bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(d_z, z, k * 32, hipMemcpyHostToDevice, ctx->stream));
+  rc = vrfhip_kzg_open_evals_batch_dev(ctx, srs, dom, k, d_c, d_z, d_v, d_o, proof_xy ? d_xy : nullptr, d_st, ctx->stream);
+  HIP_TRY(hipMemsetAsync(d_c, 0, bytes, ctx->stream));                    // staged columns
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(value, d_v, k * 32, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipMemcpyAsync(proof48, d_o, k * 48, hipMemcpyDeviceToHost, ctx->stream));

@@ -161,4 +161,27 @@ void launch_kzg_commit(const G1MsmLayout& L, const uint8_t* coeffs, uint8_t* out
 void launch_kzg_open(const G1MsmLayout& L, uint32_t* wg_sums, const uint8_t* coeffs, const uint8_t* z, uint8_t* value,
                      uint8_t* proof48, uint8_t* proof_xy, uint8_t* status, hipStream_t st, hipEvent_t* ev = nullptr);
 
+// Radix-2 transforms over Fr on a resident domain (k_fr_ntt.hip, fr_ntt.cuh).  The tables of a domain of size n = 2^log_n,
+// 9-limb Montgomery images: w [n] = w^i; for a coset off [n] = offset^i and offi [n] = n^-1 offset^-i (both nullptr for the
+// plain domain); consts: n^-1 | offset | offset^-1.
+struct FrNttTables {
+  uint32_t log_n;
+  uint32_t *w, *off, *offi, *consts;
+};
+int fr_ntt_passes(uint32_t log_n);                        // launches of one transform
+int fr_ntt_max_log();
+size_t fr_ntt_table_words(uint32_t log_n);                // words of one table
+size_t fr_ntt_const_words();
+// d_offset32 (device, nullable = 1): 32 bytes little-endian, nonzero and < r (the caller has checked)
+void launch_fr_domain_fill(const FrNttTables& T, const uint8_t* d_offset32, hipStream_t st);
+// k columns of n scalars (32 B little-endian), natural order in and out; in == out allowed.  scratch: k n 32 B, read and
+// written only by a plan of more than one pass (it then holds functions of the columns: the callers wipe it).
+// status[c] = 0 / 2 (a scalar >= r: the column's output is zero).  k * tiles < 2^31.
+void launch_fr_ntt(const FrNttTables& T, size_t k, bool inverse, const uint8_t* in, uint8_t* out, uint8_t* scratch,
+                   uint8_t* status, hipStream_t st);
+// after launch_kzg_commit / launch_kzg_open on the inverse transforms of k columns: a column with ntt_status != 0 gets
+// status 2 and zeroed outputs (out_xy, value nullable)
+void launch_fr_ntt_merge(size_t k, const uint8_t* ntt_status, uint8_t* out48, uint8_t* out_xy, uint8_t* value, uint8_t* status,
+                         hipStream_t st);
+
 }  // namespace vrf

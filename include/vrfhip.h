@@ -170,7 +170,8 @@ typedef struct vrfhip_keyset vrfhip_keyset;
 /* Library / context ------------------------------------------------------------------- */
 
 /* ABI version of this header (major*100 + minor).  vrfhip_g1_srs_*, vrfhip_kzg_commit_batch* and vrfhip_kzg_open_batch* came
- * in under 146: they only add entry points, nothing that existed changed. */
+ * in under 146: they only add entry points, nothing that existed changed.  So did vrfhip_fr_domain_*, vrfhip_fr_ntt_batch*,
+ * vrfhip_kzg_commit_evals_batch* and vrfhip_kzg_open_evals_batch*: the version stays 146. */
 int32_t vrfhip_abi_version(void);
 
 /* Last error text for this thread ("" if none). */
@@ -628,7 +629,8 @@ int32_t vrfhip_kzg_check_batch_rlc_dev(vrfhip_ctx* ctx, size_t n, const uint8_t*
  * ark-poly-commit, the producer side of the checks above.  Both are defined by the arithmetic alone: with bases [tau^j] G the
  * commitment of p is [p(tau)] G and the proof of p(z) = v is [(p(tau) - v) / (tau - z)] G; with Lagrange bases the same sums
  * commit to evaluations.  The hiding form (`rand`, `gamma_g`, a blinding polynomial) is out of scope, as are multi-point
- * openings, basis conversion, the ring's column layout and its transcript.
+ * openings, the ring's column layout and its transcript.  Columns held as evaluations over a power-of-two domain go through
+ * the transforms and the _evals forms further down.
  *
  * vrfhip_g1_srs_create: points48 = n x 48 B (host) in the compressed form vrfhip_g1_decode_batch reads, decoded with the
  * checked semantics (on the curve and in the subgroup of order r) and kept as Montgomery affine coordinates in 128-byte
@@ -684,6 +686,59 @@ int32_t vrfhip_kzg_open_batch(vrfhip_ctx* ctx, const void* srs, size_t k, size_t
 int32_t vrfhip_kzg_open_batch_dev(vrfhip_ctx* ctx, const void* srs, size_t k, size_t len, const uint8_t* d_coeffs,
                                   const uint8_t* d_z, uint8_t* d_value, uint8_t* d_proof48, uint8_t* d_proof_xy,
                                   uint8_t* d_status, void* stream);
+
+/* Radix-2 transforms over Fr of BLS12-381 on a domain that stays on the device -- `Radix2EvaluationDomain` of ark-poly: `fft`,
+ * `ifft`, `coset_fft`, `coset_ifft` -- and commitments and openings of polynomials given as EVALUATIONS over such a domain.
+ * A ring builder or prover holds its columns as evaluations; these calls interpolate, commit and open without the columns
+ * leaving the device, and evaluate on a coset of a larger domain for the quotient.
+ *
+ * vrfhip_fr_domain_create: the domain of size n = 2^log_n, log_n <= 20.  group_gen is w = TWO_ADIC_ROOT_OF_UNITY^(2^(32 -
+ * log_n)) with ark-ff's constants of Fr (TWO_ADICITY = 32, GENERATOR = 7), element i is offset * w^i.  offset32: 32 bytes
+ * little-endian (host), NULL = 1, the plain domain; otherwise `get_coset(offset)`.  VRFHIP_ERR_BAD_ARG for offset = 0, an
+ * offset >= r, log_n > 20.  The handle keeps in HBM, all computed by a kernel: the n powers w^i as Montgomery images (the
+ * inverse transform reads w^(n - i) from the same table), n^-1, and for a coset the n powers of the offset and the n values
+ * n^-1 offset^-i.  _size: n; _bytes: the HBM it holds (36 n, or 108 n for a coset, + 108).  The handle belongs to the context:
+ * destroy it before the context, as a key set or a base set.
+ *
+ * vrfhip_fr_ntt_batch*: k columns of n scalars, k x n x 32 B little-endian, natural order on both sides.
+ *     forward:                       out[c][i] = p_c(offset * w^i),  in[c][j] the coefficient of X^j        (fft / coset_fft)
+ *     flags = VRFHIP_NTT_INVERSE:    the coefficients of the polynomial of degree < n with those values   (ifft / coset_ifft)
+ * Forward then inverse is the identity, bit for bit.  status[c]: 0, or 2 if a scalar of column c is >= r -- then the whole
+ * output column is zero and the other columns are unaffected.  d_out == d_in is allowed.  k >= 1.  A column of up to 2^11
+ * scalars is one kernel launch with the column in LDS; up to 2^16 two, above three (vrfhip_test_fr_ntt_passes), with the bit
+ * reversal folded into the last pass's addressing and the scalings (offset^j, n^-1 offset^-i) into the first load and last
+ * store.  A transform of more than one pass stages the columns in the context's MSM workspace and wipes them after.
+ *
+ * vrfhip_kzg_commit_evals_batch* / vrfhip_kzg_open_evals_batch*: the inverse transform of the k columns into a coefficient
+ * region of the workspace, then vrfhip_kzg_commit_batch* (len = n, first = 0) / vrfhip_kzg_open_batch* (len = n) as they are:
+ * the same launch groups, statuses and outputs.  n = the domain's size must be <= the base set's, else VRFHIP_ERR_BAD_ARG.
+ * An evaluation >= r gives status 2 and zeroed outputs for that column.  z may be any scalar < r; a z inside the domain gives
+ * back the evaluation itself as value.  The coefficient region is witness data and is wiped with the digit, list and
+ * partial-sum regions: before a host form returns, at the end of the enqueued work for a _dev form.
+ *
+ * The handle is an opaque pointer, spelled void* in the prototypes: *out of _create, dom everywhere else.
+ * Device arrays 4-byte aligned.  VRFHIP_ERR_UNSUPPORTED on a secp256r1 context; VRFHIP_ERR_BAD_ARG for a NULL handle or one of
+ * another context, an unknown flag bit, k = 0, a NULL array that would be read or written. */
+#define VRFHIP_NTT_INVERSE 1u
+int32_t vrfhip_fr_domain_create(vrfhip_ctx* ctx, uint32_t log_n, const uint8_t* offset32, void** out);
+void vrfhip_fr_domain_destroy(void* dom);
+size_t vrfhip_fr_domain_size(const void* dom);
+size_t vrfhip_fr_domain_bytes(const void* dom);
+/* Test hook: the passes (kernel launches) one transform of size 2^log_n runs on this device.  > 0, or an error. */
+int32_t vrfhip_test_fr_ntt_passes(vrfhip_ctx* ctx, uint32_t log_n);
+int32_t vrfhip_fr_ntt_batch(vrfhip_ctx* ctx, const void* dom, size_t k, uint32_t flags, const uint8_t* in, uint8_t* out,
+                            uint8_t* status);
+int32_t vrfhip_fr_ntt_batch_dev(vrfhip_ctx* ctx, const void* dom, size_t k, uint32_t flags, const uint8_t* d_in, uint8_t* d_out,
+                                uint8_t* d_status, void* stream);
+int32_t vrfhip_kzg_commit_evals_batch(vrfhip_ctx* ctx, const void* srs, const void* dom, size_t k, const uint8_t* evals,
+                                      uint8_t* out48, uint8_t* out_xy, uint8_t* status);
+int32_t vrfhip_kzg_commit_evals_batch_dev(vrfhip_ctx* ctx, const void* srs, const void* dom, size_t k, const uint8_t* d_evals,
+                                          uint8_t* d_out48, uint8_t* d_out_xy, uint8_t* d_status, void* stream);
+int32_t vrfhip_kzg_open_evals_batch(vrfhip_ctx* ctx, const void* srs, const void* dom, size_t k, const uint8_t* evals,
+                                    const uint8_t* z, uint8_t* value, uint8_t* proof48, uint8_t* proof_xy, uint8_t* status);
+int32_t vrfhip_kzg_open_evals_batch_dev(vrfhip_ctx* ctx, const void* srs, const void* dom, size_t k, const uint8_t* d_evals,
+                                        const uint8_t* d_z, uint8_t* d_value, uint8_t* d_proof48, uint8_t* d_proof_xy,
+                                        uint8_t* d_status, void* stream);
 
 /* Multi-commitment, multi-point KZG openings -- the shape a ring proof ends in (as far as upstream is recalled, INTEGRATION.md
  * section 4): the verifier folds its proof's column commitments and fixed columns of its key into aggregate commitments, opens

@@ -740,6 +740,81 @@ std::vector<OpeningProof> open_batch(const Context<S>& ctx, const Srs<S>& srs, c
   }
   return r;
 }
+
+// Columns held as EVALUATIONS over a power-of-two domain: `Radix2EvaluationDomain` of ark-poly resident in HBM
+// (vrfhip_fr_domain), its transforms (vrfhip_fr_ntt_batch), and commit / open from evaluations.
+template <class S>
+class Domain {
+ public:
+  // the plain domain of size 2^log_n
+  Domain(const Context<S>& ctx, uint32_t log_n) {
+    check(vrfhip_fr_domain_create(ctx.handle(), log_n, nullptr, &h_), "vrfhip_fr_domain_create");
+  }
+  // `get_coset(offset)`: 0 < offset < r
+  Domain(const Context<S>& ctx, uint32_t log_n, const Scalar& offset) {
+    check(vrfhip_fr_domain_create(ctx.handle(), log_n, offset.data(), &h_), "vrfhip_fr_domain_create");
+  }
+  ~Domain() { vrfhip_fr_domain_destroy(h_); }
+  Domain(const Domain&) = delete;
+  Domain& operator=(const Domain&) = delete;
+  const void* handle() const { return h_; }            // the opaque vrfhip_fr_domain handle
+  size_t size() const { return vrfhip_fr_domain_size(h_); }
+  size_t bytes() const { return vrfhip_fr_domain_bytes(h_); }
+
+ private:
+  void* h_ = nullptr;
+};
+struct Column { std::vector<Scalar> values; Result status; };
+// `fft` / `coset_fft` of every column (inverse: `ifft` / `coset_ifft`); all columns have the domain's size
+template <class S>
+std::vector<Column> ntt_batch(const Context<S>& ctx, const Domain<S>& dom, const std::vector<std::vector<Scalar>>& columns,
+                              bool inverse = false) {
+  const size_t k = columns.size(), n = dom.size();
+  const Bytes flat = detail_kzg::flatten(columns, n);
+  Bytes out(k * n * 32 + 1), st(k + 1);
+  check(vrfhip_fr_ntt_batch(ctx.handle(), dom.handle(), k, inverse ? VRFHIP_NTT_INVERSE : 0u, flat.data(), out.data(), st.data()),
+        "vrfhip_fr_ntt_batch");
+  std::vector<Column> r(k);
+  for (size_t c = 0; c < k; ++c) {
+    r[c].values.resize(n);
+    for (size_t j = 0; j < n; ++j) std::memcpy(r[c].values[j].data(), out.data() + (c * n + j) * 32, 32);
+    r[c].status = result_of(st[c]);
+  }
+  return r;
+}
+// commit_batch of the polynomials that take these values over dom
+template <class S>
+std::vector<Commitment> commit_evals_batch(const Context<S>& ctx, const Srs<S>& srs, const Domain<S>& dom,
+                                           const std::vector<std::vector<Scalar>>& evals) {
+  const size_t k = evals.size();
+  const Bytes flat = detail_kzg::flatten(evals, dom.size());
+  Bytes out(48 * k + 1), st(k + 1);
+  check(vrfhip_kzg_commit_evals_batch(ctx.handle(), srs.handle(), dom.handle(), k, flat.data(), out.data(), nullptr, st.data()),
+        "vrfhip_kzg_commit_evals_batch");
+  std::vector<Commitment> r(k);
+  for (size_t c = 0; c < k; ++c) { std::memcpy(r[c].point.data(), out.data() + 48 * c, 48); r[c].status = result_of(st[c]); }
+  return r;
+}
+// open_batch of the polynomials that take these values over dom, polynomial c at points[c]
+template <class S>
+std::vector<OpeningProof> open_evals_batch(const Context<S>& ctx, const Srs<S>& srs, const Domain<S>& dom,
+                                           const std::vector<std::vector<Scalar>>& evals, const std::vector<Scalar>& points) {
+  const size_t k = evals.size();
+  if (points.size() != k) throw std::invalid_argument("one point per polynomial");
+  const Bytes flat = detail_kzg::flatten(evals, dom.size());
+  Bytes z(32 * k + 1), v(32 * k + 1), out(48 * k + 1), st(k + 1);
+  for (size_t c = 0; c < k; ++c) std::memcpy(z.data() + 32 * c, points[c].data(), 32);
+  check(vrfhip_kzg_open_evals_batch(ctx.handle(), srs.handle(), dom.handle(), k, flat.data(), z.data(), v.data(), out.data(),
+                                    nullptr, st.data()),
+        "vrfhip_kzg_open_evals_batch");
+  std::vector<OpeningProof> r(k);
+  for (size_t c = 0; c < k; ++c) {
+    std::memcpy(r[c].value.data(), v.data() + 32 * c, 32);
+    std::memcpy(r[c].proof.data(), out.data() + 48 * c, 48);
+    r[c].status = result_of(st[c]);
+  }
+  return r;
+}
 }  // namespace kzg
 
 }  // namespace ark_vrf_hip

@@ -760,6 +760,20 @@ def gen_field0():
     ap("// (beta x, y) = -[x^2] (x, y) on the prime-order subgroup (checked on the generator; the other root fails)")
     ap(carr("BLS_EXP_SQRT", [((bl["P"] + 1) // 4 >> (32 * i)) & 0xFFFFFFFF for i in range(12)]))
     ap(carr("BLS_BETA_M", bl["lim"](bl["mont"](bl["beta"]))))
+    # ---- radix-2 domains (fr_ntt.cuh): what ark-ff's Fr of ark-bls12-381 states ----
+    two_adicity, gen = 32, 7
+    assert (Q - 1) % (1 << two_adicity) == 0 and (Q - 1) % (1 << (two_adicity + 1)) != 0, "2-adicity of r - 1"
+    root = pow(gen, (Q - 1) >> two_adicity, Q)
+    assert root == 0x16a2a19edfe81f20d09b681922c813b4b63683508c2280b93829971f439f0d2b, "TWO_ADIC_ROOT_OF_UNITY"
+    assert pow(root, 1 << (two_adicity - 1), Q) == Q - 1, "the root has order exactly 2^32"
+    ap("// ---- radix-2 evaluation domains (fr_ntt.cuh): ark-ff's FftField constants of Fr ----")
+    ap("constexpr int FR_TWO_ADICITY = %d;" % two_adicity)
+    ap("constexpr uint32_t FR_GENERATOR = %du;" % gen)
+    ap(carr("FR_TWO_ADIC_ROOT32", words32(root)))
+    ap(carr("FR_TWO_ADIC_ROOT_M", F.lm(root)))
+    ap(carr("FR_INV2_M", F.lm(inv(2))))
+    ap("// 2q in exact 29-bit limbs: the modulus of the butterflies' conditional subtraction")
+    ap(carr("FR_TWOQ29", F.limbs(2 * Q)))
     emit_field_traits(ap, F, st)
     emit_tables(ap, F, st, [("BS_G_XY", (BS["gx"], BS["gy"])), ("BS_B_XY", (BS["bx"], BS["by"])),
                             ("JJ_G_XY", (JJ["gx"], JJ["gy"])), ("JJ_B_XY", (jbx, jby))])
