@@ -6,16 +6,8 @@
 // Pippenger with signed 11-bit windows (msm.cuh).
 //   k_msm_prep    : bases -> Montgomery affine-cached (x, y, d*x*y); scalars -> signed digits
 //   k_msm_buckets : one workgroup per (window, point-group); the 1024 buckets of the window live in LDS.
-//                   The workgroup counting-sorts its points by bucket (LDS atomics + wave-shuffle block
-//                   scan), then the sorted list is cut into 512 EQUAL chunks, one per lane: every lane
-//                   performs the same number of mixed additions whatever the digit distribution.  A
-//                   lane keeps the running sum of the current bucket in registers and flushes it when
-//                   the bucket changes: runs that start inside the chunk go straight to their LDS
-//                   bucket (exactly one lane owns the start of a bucket), the first run of a chunk --
-//                   possibly the continuation of the previous lane's bucket -- is parked as a "head"
-//                   and merged afterwards by the first lane of each chain.  Then the 1024 buckets are
-//                   reduced to sum_j j*B_j inside the workgroup: pair-local sums, a suffix scan and a
-//                   tree reduction over 512 lanes staged through LDS.
+//                   The bucket pass of msm_buckets.cuh with two buckets per lane: counting sort by bucket, the sorted
+//                   list cut into 512 equal chunks, heads merged, sum_j j*B_j inside the workgroup.
 //   k_msm_final   : sums the groups of every window, shifts window w by 11*w doublings (one DPP quad per
 //                   window, the quad's lanes share each doubling), tree-sums the windows, encodes.
 #include "kernels.h"
@@ -61,16 +53,29 @@ VRF_HD PtE lds_load_pt(const uint32_t* src) {
   return p;
 }
 
-constexpr uint32_t MSM_NONE = 0xffffffffu;
+// the twisted-Edwards instantiation of msm_bucket_pass (msm_buckets.cuh): extended accumulators, affine-cached inputs, two
+// buckets per lane.  TeMsmShape is what the host side needs of it.
+struct TeMsmShape {
+  static constexpr int BLOCK = MSM_BLOCK, BPL = MSM_BPL, PT_WORDS = MSM_PT_WORDS, AFF_STRIDE = MSM_PTA_STRIDE, IDX_BITS = MSM_IDX_BITS;
+  static constexpr int HIST_LOADS = 4, SCATTER_LOADS = 4;
+};
+template <class S>
+struct TeMsm : TeMsmShape {
+  using Acc = PtE;
+  using Aff = PtA;
+  static VRF_HD PtE identity() { return te_identity(); }
+  static VRF_HD PtE load(const uint32_t* src) { return lds_load_pt(src); }
+  static VRF_HD void store(uint32_t* dst, const PtE& p) { lds_store_pt(dst, p); }
+  static VRF_HD PtA aff_load(const uint32_t* src) { return pta_load(src); }
+  static VRF_HD PtA aff_identity() { return pta_identity(); }
+  static VRF_HD PtE madd(const PtE& p, const PtA& q, bool neg) { return te_add_affine<S>(p, q, neg); }
+  static VRF_HD PtE add(const PtE& p, const PtE& q) { return te_add<S>(p, q); }
+  static VRF_HD PtE dbl(const PtE& p) { return te_dbl<S>(p, true); }
+};
 
 template <class S>
 __global__ void __launch_bounds__(MSM_BLOCK) k_msm_buckets(MsmLayout L) {
   extern __shared__ uint32_t lds[];
-  uint32_t* bucket = lds;                                   // [MSM_BUCKETS][36] bucket accumulators (147,456 B)
-  uint32_t* counts = lds + MSM_BUCKETS * MSM_PT_WORDS;      // [1024] bucket sizes
-  uint32_t* cursor = counts + MSM_BUCKETS;                  // [1024] scatter cursors, later head bucket ids
-  uint32_t* wsum = cursor + MSM_BUCKETS;                    // [8] per-wave totals for the block scan
-  const int t = threadIdx.x;
   // low windows (all points) first, then the high windows (only the points with full-size scalars)
   // GROUP-major: consecutive workgroups are the windows of ONE point group, so the workgroups that run at the same time
   // gather from the same few slices of the point array and find each other's lines in the Infinity Cache / L2 (window-major
@@ -84,172 +89,14 @@ __global__ void __launch_bounds__(MSM_BLOCK) k_msm_buckets(MsmLayout L) {
   const size_t span = low ? L.per_group : L.per_group_hi, end = low ? L.n : L.n_long;
   const size_t lo = (size_t)g * span;
   const size_t hi = lo + span < end ? lo + span : end;
-  const uint32_t cnt_all = lo < hi ? (uint32_t)(hi - lo) : 0u;
-  const int16_t* dig = L.digits + (size_t)w * L.n + lo;
-  const uint32_t* P = L.pts + lo * MSM_PTA_STRIDE;
-  uint32_t* list = L.lists + (size_t)wg * L.list_cap;
-  uint32_t* heads = L.heads + (size_t)wg * MSM_BLOCK * MSM_PT_WORDS;
-  {
-    PtE id = te_identity();
-#pragma unroll
-    for (int u = 0; u < MSM_BPL; ++u) lds_store_pt(bucket + (MSM_BPL * t + u) * MSM_PT_WORDS, id);
-  }
-  // 1. histogram of the group's digits
-#pragma unroll
-  for (int u = 0; u < MSM_BPL; ++u) counts[t + u * MSM_BLOCK] = 0;
-  __syncthreads();
-  // four independent digit loads per trip keep the memory pipe busy (a lane's trip is latency-bound)
-  for (uint32_t j0 = t; j0 < cnt_all; j0 += 4 * MSM_BLOCK) {
-    int d[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const uint32_t j = j0 + u * MSM_BLOCK;
-      d[u] = j < cnt_all ? dig[j] : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (d[u] != 0) atomicAdd(&counts[(d[u] < 0 ? -d[u] : d[u]) - 1], 1u);
-  }
-  __syncthreads();
-  // 2. exclusive scan over 1024 counts: lane t scans its pair, waves scan by shuffles
-  uint32_t m;
-  {
-    uint32_t c0 = counts[MSM_BPL * t], c1 = MSM_BPL == 2 ? counts[MSM_BPL * t + MSM_BPL - 1] : 0u;
-    uint32_t v = c0 + c1, incl = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-      uint32_t u = __shfl_up(incl, s, 64);
-      if ((t & 63) >= s) incl += u;
-    }
-    if ((t & 63) == 63) wsum[t >> 6] = incl;
-    __syncthreads();
-    uint32_t wbase = 0, total = 0;
-    for (int k = 0; k < MSM_BLOCK / 64; ++k) {
-      uint32_t x = wsum[k];
-      if (k < (t >> 6)) wbase += x;
-      total += x;
-    }
-    m = total;
-    uint32_t excl = wbase + incl - v;
-    cursor[MSM_BPL * t] = excl;
-    if (MSM_BPL == 2) cursor[MSM_BPL * t + MSM_BPL - 1] = excl + c0;
-  }
-  __syncthreads();
-  // 3. scatter into bucket order, transposed so that entry i of lane l sits at list[i*512 + l]
-  const uint32_t chunk = (m + MSM_BLOCK - 1) / MSM_BLOCK;
-  for (uint32_t j0 = t; j0 < cnt_all; j0 += 4 * MSM_BLOCK) {
-    int dd[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const uint32_t j = j0 + u * MSM_BLOCK;
-      dd[u] = j < cnt_all ? dig[j] : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int d = dd[u];
-      const uint32_t j = j0 + u * MSM_BLOCK;
-      if (d != 0) {
-        uint32_t b = (uint32_t)(d < 0 ? -d : d) - 1;
-        uint32_t pos = atomicAdd(&cursor[b], 1u);
-        uint32_t lane = pos / chunk, i = pos - lane * chunk;
-        list[(size_t)i * MSM_BLOCK + lane] = j | (b << MSM_IDX_BITS) | (d < 0 ? 0x80000000u : 0u);
-      }
-    }
-  }
-  __threadfence_block();
-  __syncthreads();
-  // 4. every lane folds its chunk; same trip count for all lanes
-  uint32_t head_b = MSM_NONE;
-  {
-    const uint32_t my0 = (uint32_t)t * chunk;
-    const uint32_t cnt = my0 >= m ? 0u : (m - my0 < chunk ? m - my0 : chunk);
-    PtE acc = te_identity();
-    uint32_t cur = MSM_NONE;
-    bool first_run = true;
-    uint32_t* myhead = heads + (size_t)t * MSM_PT_WORDS;
-    // Two loads feed an addition -- the list entry, then the point it names -- and the second address depends on the first:
-    // entries are fetched TWO trips ahead and points one trip ahead, so that neither latency is exposed (with both one
-    // trip ahead the gather waited for its own index: 0.70 of the issue slots).
-    uint32_t ent_n = 0, ent_nn = 0;
-    PtA pa_n = pta_identity();
-    if (cnt > 0) ent_n = list[t];
-    if (cnt > 1) ent_nn = list[(size_t)MSM_BLOCK + t];
-    if (cnt > 0) pa_n = pta_load(P + (size_t)(ent_n & MSM_IDX_MASK) * MSM_PTA_STRIDE);
-#pragma unroll 1
-    for (uint32_t i = 0; i < chunk; ++i) {
-      if (i < cnt) {
-        const uint32_t ent = ent_n;
-        const PtA pa = pa_n;
-        ent_n = ent_nn;
-        if (i + 2 < cnt) ent_nn = list[(size_t)(i + 2) * MSM_BLOCK + t];
-        if (i + 1 < cnt) pa_n = pta_load(P + (size_t)(ent_n & MSM_IDX_MASK) * MSM_PTA_STRIDE);
-        const uint32_t b = (ent >> MSM_IDX_BITS) & (MSM_BUCKETS - 1);
-        if (b != cur) {
-          if (cur != MSM_NONE) {
-            if (first_run) { lds_store_pt(myhead, acc); head_b = cur; first_run = false; }
-            else lds_store_pt(bucket + cur * MSM_PT_WORDS, acc);
-          }
-          cur = b;
-          acc = te_identity();
-        }
-        acc = te_add_affine<S>(acc, pa, (ent >> 31) != 0);
-      }
-    }
-    if (cnt > 0) {
-      if (first_run) { lds_store_pt(myhead, acc); head_b = cur; }
-      else lds_store_pt(bucket + cur * MSM_PT_WORDS, acc);
-    }
-  }
-  cursor[t] = head_b;
-  __threadfence_block();
-  __syncthreads();
-  // 5. merge the heads: the first lane of each chain of equal head buckets adds the chain to the bucket
-  if (head_b != MSM_NONE && (t == 0 || cursor[t - 1] != head_b)) {
-    PtE h = lds_load_pt(heads + (size_t)t * MSM_PT_WORDS);
-    for (int k = t + 1; k < MSM_BLOCK && cursor[k] == head_b; ++k)
-      h = te_add<S>(h, lds_load_pt(heads + (size_t)k * MSM_PT_WORDS));
-    uint32_t* slot = bucket + head_b * MSM_PT_WORDS;
-    lds_store_pt(slot, te_add<S>(lds_load_pt(slot), h));
-  }
-  __syncthreads();
-  // ---- bucket reduction: R = sum_j j*B_j.  One bucket per lane (10-bit windows): lane t holds B_{t+1}; a suffix scan gives
-  // S_t = sum_{u >= t} B_{u+1} and R = sum_t S_t.  Two per lane (11-bit): S_t = B_{2t+1} + B_{2t+2}, L_t = S_t + B_{2t+2},
-  // R = sum_t L_t + 2 sum_{t >= 1} Suf_t with Suf the suffix sums of S.  The staging area re-uses the bucket storage. ----
-  PtE Ssum, V;
-  if (MSM_BPL == 2) {
-    PtE b1 = lds_load_pt(bucket + (2 * t + 1) * MSM_PT_WORDS);
-    Ssum = te_add<S>(lds_load_pt(bucket + (2 * t) * MSM_PT_WORDS), b1);
-    V = te_add<S>(Ssum, b1);                      // L_t
-  } else {
-    Ssum = lds_load_pt(bucket + t * MSM_PT_WORDS);
-    V = te_identity();
-  }
-  __syncthreads();
-  uint32_t* stage = lds;                          // [MSM_BLOCK][36]
-  // pass 0: suffix scan of S (Hillis-Steele);  pass 1: tree reduction
-#pragma unroll 1
-  for (int pass = 0; pass < 2; ++pass) {
-    PtE cur = pass == 0 ? Ssum : V;
-#pragma unroll 1
-    for (int k = 0; k < MSM_LOG2_BLOCK; ++k) {
-      const int s = pass == 0 ? (1 << k) : (MSM_BLOCK >> (k + 1));
-      __syncthreads();
-      lds_store_pt(stage + t * MSM_PT_WORDS, cur);
-      __syncthreads();
-      const bool active = pass == 0 ? (t + s < MSM_BLOCK) : (t < s);
-      if (active) cur = te_add<S>(cur, lds_load_pt(stage + (t + s) * MSM_PT_WORDS));
-    }
-    if (pass == 0) {
-      if (MSM_BPL == 2) {
-        if (t >= 1) V = te_add<S>(V, te_dbl<S>(cur, true));
-      } else {
-        V = cur;                                  // S_t: the tree below sums them
-      }
-    } else {
-      V = cur;
-    }
-  }
-  if (t == 0) lds_store_pt(L.part + ((size_t)w * L.groups + g) * MSM_PT_WORDS, V);
+  MsmBucketJob job;
+  job.digits = L.digits + (size_t)w * L.n + lo;
+  job.pts = L.pts + lo * MSM_PTA_STRIDE;
+  job.count = lo < hi ? (uint32_t)(hi - lo) : 0u;
+  job.list = L.lists + (size_t)wg * L.list_cap;
+  job.heads = L.heads + (size_t)wg * MSM_BLOCK * MSM_PT_WORDS;
+  job.out = L.part + ((size_t)w * L.groups + g) * MSM_PT_WORDS;
+  msm_bucket_pass<TeMsm<S>>(job, lds);
 }
 
 // ------------------------------------------------------------------------------- final
@@ -406,8 +253,6 @@ __global__ void __launch_bounds__(MSM_FINAL_BLOCK) k_msm_final(const uint32_t* p
 }
 
 // ------------------------------------------------------------------------------- host
-static size_t pad256(size_t x) { return (x + 255) & ~size_t(255); }
-
 // high-window groups for `groups` low-window groups: proportional to the share of full-size scalars
 static int msm_groups_hi(size_t n, size_t n_long, int groups) {
   if (n_long >= n) return groups;
@@ -435,22 +280,32 @@ int msm_groups(size_t n, size_t n_long, int cus) {
   return g;
 }
 
+// the regions of an MSM over n points in `groups` groups, sized for the worst case groups_hi == groups
+static void msm_carve(MsmCarve& c, MsmLayout& L, size_t n, int groups) {
+  L.per_group = (n + groups - 1) / groups;
+  L.list_cap = L.per_group + MSM_BLOCK;
+  const MsmRegions r = msm_carve_regions<TeMsmShape>(c, n, MSM_W, n, (size_t)MSM_W * groups, L.list_cap);
+  L.pts = r.pts; L.digits = r.digits; L.lists = r.lists; L.heads = r.heads; L.part = r.part;
+  L.flags = c.take<uint8_t>(256);
+}
+
 size_t msm_workspace_bytes(size_t n, int groups) {
-  // sized for the worst case groups_hi == groups
-  size_t per_group = (n + groups - 1) / groups, list_cap = per_group + MSM_BLOCK, wgs = (size_t)MSM_W * groups;
-  return pad256(n * MSM_PTA_STRIDE * 4) + pad256((size_t)MSM_W * n * 2) + pad256(wgs * list_cap * 4) +
-         pad256(wgs * MSM_BLOCK * MSM_PT_WORDS * 4) + pad256(wgs * MSM_PT_WORDS * 4) + 256;
+  MsmLayout L;
+  MsmCarve c(nullptr);
+  msm_carve(c, L, n, groups);
+  return c.off;
 }
 
 MsmLayout msm_layout(size_t n, size_t n_long, int groups, void* ws) {
   MsmLayout L;
+  MsmCarve c(ws);
+  msm_carve(c, L, n, groups);
   L.sflags = 0;
   L.n = n;
   L.n_long = n_long < n ? n_long : n;
   L.groups = groups;
   L.groups_hi = msm_groups_hi(n, L.n_long, groups);
   if (L.groups_hi > groups) L.groups_hi = groups;
-  L.per_group = (n + groups - 1) / groups;
   L.per_group_hi = (L.n_long + L.groups_hi - 1) / L.groups_hi;
   // groups_hi rounds to nearest, so a high-window group can be slightly larger than a low-window one;
   // the list capacity was sized for per_group: keep within it
@@ -458,22 +313,13 @@ MsmLayout msm_layout(size_t n, size_t n_long, int groups, void* ws) {
     ++L.groups_hi;
     L.per_group_hi = (L.n_long + L.groups_hi - 1) / L.groups_hi;
   }
-  L.list_cap = L.per_group + MSM_BLOCK;
-  const size_t wgs = (size_t)MSM_W * groups;
-  uint8_t* p = static_cast<uint8_t*>(ws);
-  L.pts = reinterpret_cast<uint32_t*>(p); p += pad256(n * MSM_PTA_STRIDE * 4);
-  L.digits = reinterpret_cast<int16_t*>(p); p += pad256((size_t)MSM_W * n * 2);
-  L.lists = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * L.list_cap * 4);
-  L.heads = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * MSM_BLOCK * MSM_PT_WORDS * 4);
-  L.part = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * MSM_PT_WORDS * 4);
-  L.flags = p;
   return L;
 }
 
 template <class S>
 static void launch_msm_core_t(const MsmLayout& L, uint8_t* out_enc, uint8_t* out_xy, uint8_t* status,
                               uint8_t* fail_flag, hipStream_t st, hipEvent_t* ev) {
-  const size_t lds_bytes = ((size_t)MSM_BUCKETS * MSM_PT_WORDS + 2 * MSM_BUCKETS + 16) * 4;   // 155,712 B of 160 KiB
+  const size_t lds_bytes = msm_bucket_lds_bytes<TeMsm<S>>();   // 155,712 B of 160 KiB
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_msm_buckets<S>),

@@ -9,14 +9,11 @@
 // bucket accumulation staged in LDS):
 //   k_g1_prep_rlc / k_g1_prep_msm : wire points -> Montgomery affine, on-curve test; weights or scalars -> signed
 //                                   10-bit digits
-//   k_g1_buckets : one workgroup per (set, window, point group) owns the window's 512 buckets in LDS (84 KiB).
-//                  Counting sort of the group's points by bucket (LDS atomics, wave-shuffle scan), the sorted list
-//                  is cut into 512 equal chunks, every lane folds its chunk with complete mixed additions and
-//                  flushes a run when the bucket changes (first run parked as a "head" and merged afterwards), then
-//                  sum_j j B_j by a suffix scan and a tree over the 512 lanes, staged through LDS.
+//   k_g1_buckets : one workgroup per (set, window, point group) owns the window's 512 buckets in LDS (84 KiB): the
+//                  bucket pass of msm_buckets.cuh with complete mixed additions.
 //   k_g1_final   : per set, one QUAD per window: sum of the groups, 10 w doublings (two rounds of one product per lane
 //                  each), tree-sum, affine, wire format.
-// Same schedule as k_msm.hip (twisted Edwards); the group law is g1.cuh's complete projective one.
+// The group law is g1.cuh's complete projective one.
 #include "msm_g1.h"
 
 #include "g1.cuh"
@@ -95,144 +92,46 @@ __global__ void __launch_bounds__(128) k_g1_prep_msm(G1MsmLayout L, const uint8_
 }
 
 // ------------------------------------------------------------------------------- buckets
-constexpr uint32_t G1_NONE = 0xffffffffu;
-constexpr uint32_t G1_IDX_MASK = (1u << G1_IDX_BITS) - 1;
+// the G1 instantiation of msm_bucket_pass (msm_buckets.cuh): projective accumulators, affine (x, y) inputs that are never the
+// point at infinity (its digits are zero)
+struct G1MsmAff { FpS x, y; };
+struct G1Msm {
+  using Acc = G1P;
+  using Aff = G1MsmAff;
+  static constexpr int BLOCK = G1_BLOCK, BPL = 1, PT_WORDS = G1_PT_WORDS, AFF_STRIDE = G1_AFF_STRIDE, IDX_BITS = G1_IDX_BITS;
+  static constexpr int HIST_LOADS = 1, SCATTER_LOADS = 1;
+  static VRF_HD G1P identity() { return g1_identity(); }
+  static VRF_HD G1P load(const uint32_t* src) { return g1p_load(src); }
+  static VRF_HD void store(uint32_t* dst, const G1P& p) { g1p_store(dst, p); }
+  static VRF_HD G1MsmAff aff_load(const uint32_t* src) {
+    G1MsmAff a;
+#pragma unroll
+    for (int j = 0; j < NLB; ++j) { a.x.v[j] = (int32_t)src[j]; a.y.v[j] = (int32_t)src[NLB + j]; }
+    return a;
+  }
+  static VRF_HD G1MsmAff aff_identity() { return G1MsmAff{FpS(fp_zero()), FpS(fp_zero())}; }      // a placeholder, never added
+  static VRF_HD G1P madd(const G1P& p, const G1MsmAff& q, bool neg) { return g1_madd(p, q.x, q.y, neg); }
+  static VRF_HD G1P add(const G1P& p, const G1P& q) { return g1_add(p, q); }
+};
+static_assert(G1_BLOCK * G1Msm::BPL == G1_BUCKETS, "one bucket per lane");
 
 // SHARED_PTS: the sets are columns of scalars over one set of points (msm_g1.h)
 template <bool SHARED_PTS>
 __global__ void __launch_bounds__(G1_BLOCK) k_g1_buckets(G1MsmLayout L) {
   extern __shared__ uint32_t lds[];
-  uint32_t* bucket = lds;                                   // [512][42]
-  uint32_t* counts = lds + G1_BUCKETS * G1_PT_WORDS;        // [512]
-  uint32_t* cursor = counts + G1_BUCKETS;                   // [512] scatter cursors, later head bucket ids
-  uint32_t* wsum = cursor + G1_BUCKETS;                     // [8]
-  const int t = threadIdx.x;
   const int wg = blockIdx.x;
   const int per_set = L.windows * L.groups;
   const int set = wg / per_set, w = (wg % per_set) / L.groups, g = wg % L.groups;
   const size_t lo = (size_t)g * L.per_group;
   const size_t hi = lo + L.per_group < L.n ? lo + L.per_group : L.n;
-  const uint32_t cnt_all = lo < hi ? (uint32_t)(hi - lo) : 0u;
-  const int16_t* dig = L.digits + ((size_t)set * L.windows + w) * L.n + lo;
-  const uint32_t* P = L.pts + ((SHARED_PTS ? (size_t)0 : (size_t)set * L.n) + lo) * G1_AFF_STRIDE;
-  uint32_t* list = L.lists + (size_t)wg * L.list_cap;
-  uint32_t* heads = L.heads + (size_t)wg * G1_BLOCK * G1_PT_WORDS;
-  g1p_store(bucket + t * G1_PT_WORDS, g1_identity());
-  // 1. histogram
-  counts[t] = 0;
-  __syncthreads();
-  for (uint32_t j = t; j < cnt_all; j += G1_BLOCK) {
-    const int d = dig[j];
-    if (d != 0) atomicAdd(&counts[(d < 0 ? -d : d) - 1], 1u);
-  }
-  __syncthreads();
-  // 2. exclusive scan of the 512 counts: waves scan by shuffles, wave totals through LDS
-  uint32_t m;
-  {
-    const uint32_t v = counts[t];
-    uint32_t incl = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-      const uint32_t u = __shfl_up(incl, s, 64);
-      if ((t & 63) >= s) incl += u;
-    }
-    if ((t & 63) == 63) wsum[t >> 6] = incl;
-    __syncthreads();
-    uint32_t wbase = 0, total = 0;
-    for (int k = 0; k < G1_BLOCK / 64; ++k) {
-      const uint32_t x = wsum[k];
-      if (k < (t >> 6)) wbase += x;
-      total += x;
-    }
-    m = total;
-    cursor[t] = wbase + incl - v;
-  }
-  __syncthreads();
-  // 3. scatter into bucket order, transposed: entry i of lane l sits at list[i * 512 + l]
-  const uint32_t chunk = (m + G1_BLOCK - 1) / G1_BLOCK;
-  for (uint32_t j = t; j < cnt_all; j += G1_BLOCK) {
-    const int d = dig[j];
-    if (d != 0) {
-      const uint32_t b = (uint32_t)(d < 0 ? -d : d) - 1;
-      const uint32_t pos = atomicAdd(&cursor[b], 1u);
-      const uint32_t lane = pos / chunk, i = pos - lane * chunk;
-      list[(size_t)i * G1_BLOCK + lane] = j | (b << G1_IDX_BITS) | (d < 0 ? 0x80000000u : 0u);
-    }
-  }
-  __threadfence_block();
-  __syncthreads();
-  // 4. every lane folds its chunk (same trip count for all lanes)
-  uint32_t head_b = G1_NONE;
-  {
-    const uint32_t my0 = (uint32_t)t * chunk;
-    const uint32_t cnt = my0 >= m ? 0u : (m - my0 < chunk ? m - my0 : chunk);
-    G1P acc = g1_identity();
-    uint32_t cur = G1_NONE;
-    bool first_run = true;
-    uint32_t* myhead = heads + (size_t)t * G1_PT_WORDS;
-    // the list entry names the point: entries are fetched two trips ahead, points one trip ahead (k_msm.hip)
-    auto load_xy = [&](FpS& x, FpS& y, uint32_t e) {
-      const uint32_t* src = P + (size_t)(e & G1_IDX_MASK) * G1_AFF_STRIDE;
-#pragma unroll
-      for (int j = 0; j < NLB; ++j) { x.v[j] = (int32_t)src[j]; y.v[j] = (int32_t)src[NLB + j]; }
-    };
-    uint32_t ent_n = 0, ent_nn = 0;
-    FpS x_n = FpS(fp_zero()), y_n = FpS(fp_zero());
-    if (cnt > 0) ent_n = list[t];
-    if (cnt > 1) ent_nn = list[(size_t)G1_BLOCK + t];
-    if (cnt > 0) load_xy(x_n, y_n, ent_n);
-#pragma unroll 1
-    for (uint32_t i = 0; i < chunk; ++i) {
-      if (i < cnt) {
-        const uint32_t ent = ent_n;
-        const FpS x = x_n, y = y_n;
-        ent_n = ent_nn;
-        if (i + 2 < cnt) ent_nn = list[(size_t)(i + 2) * G1_BLOCK + t];
-        if (i + 1 < cnt) load_xy(x_n, y_n, ent_n);
-        const uint32_t b = (ent >> G1_IDX_BITS) & (G1_BUCKETS - 1);
-        if (b != cur) {
-          if (cur != G1_NONE) {
-            if (first_run) { g1p_store(myhead, acc); head_b = cur; first_run = false; }
-            else g1p_store(bucket + cur * G1_PT_WORDS, acc);
-          }
-          cur = b;
-          acc = g1_identity();
-        }
-        acc = g1_madd(acc, x, y, (ent >> 31) != 0);
-      }
-    }
-    if (cnt > 0) {
-      if (first_run) { g1p_store(myhead, acc); head_b = cur; }
-      else g1p_store(bucket + cur * G1_PT_WORDS, acc);
-    }
-  }
-  cursor[t] = head_b;
-  __threadfence_block();
-  __syncthreads();
-  // 5. merge the heads: the first lane of each chain of equal head buckets adds the chain to the bucket
-  if (head_b != G1_NONE && (t == 0 || cursor[t - 1] != head_b)) {
-    G1P h = g1p_load(heads + (size_t)t * G1_PT_WORDS);
-    for (int k = t + 1; k < G1_BLOCK && cursor[k] == head_b; ++k) h = g1_add(h, g1p_load(heads + (size_t)k * G1_PT_WORDS));
-    uint32_t* slot = bucket + head_b * G1_PT_WORDS;
-    g1p_store(slot, g1_add(g1p_load(slot), h));
-  }
-  __syncthreads();
-  // 6. R = sum_j j B_j: lane t holds B_{t+1}; suffix scan S_t = sum_{u >= t} B_{u+1}, then R = sum_t S_t
-  G1P cur = g1p_load(bucket + t * G1_PT_WORDS);
-  uint32_t* stage = lds;
-#pragma unroll 1
-  for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll 1
-    for (int k = 0; k < 9; ++k) {
-      const int s = pass == 0 ? (1 << k) : (G1_BLOCK >> (k + 1));
-      __syncthreads();
-      g1p_store(stage + t * G1_PT_WORDS, cur);
-      __syncthreads();
-      const bool active = pass == 0 ? (t + s < G1_BLOCK) : (t < s);
-      if (active) cur = g1_add(cur, g1p_load(stage + (t + s) * G1_PT_WORDS));
-    }
-  }
-  if (t == 0) g1p_store(L.part + (((size_t)set * L.windows + w) * L.groups + g) * G1_PT_WORDS, cur);
+  MsmBucketJob job;
+  job.digits = L.digits + ((size_t)set * L.windows + w) * L.n + lo;
+  job.pts = L.pts + ((SHARED_PTS ? (size_t)0 : (size_t)set * L.n) + lo) * G1_AFF_STRIDE;
+  job.count = lo < hi ? (uint32_t)(hi - lo) : 0u;
+  job.list = L.lists + (size_t)wg * L.list_cap;
+  job.heads = L.heads + (size_t)wg * G1_BLOCK * G1_PT_WORDS;
+  job.out = L.part + (((size_t)set * L.windows + w) * L.groups + g) * G1_PT_WORDS;
+  msm_bucket_pass<G1Msm>(job, lds);
 }
 
 // ------------------------------------------------------------------------------- final
@@ -313,8 +212,6 @@ __global__ void __launch_bounds__(G1_FINAL_BLOCK) k_g1_final(G1MsmLayout L) {
 }
 
 // ------------------------------------------------------------------------------- host
-static size_t pad256(size_t x) { return (x + 255) & ~size_t(255); }
-
 int g1_msm_groups(size_t n, int sets, int windows, int cus) {
   int g = cus / (sets * windows);                 // about one round of the chip
   if (g < 1) g = 1;
@@ -325,30 +222,34 @@ int g1_msm_groups(size_t n, int sets, int windows, int cus) {
   if ((size_t)g < min_g) g = (int)min_g;
   return g;
 }
-size_t g1_msm_workspace_bytes(size_t n, int sets, int windows, int groups) {
-  const size_t per_group = (n + groups - 1) / groups, list_cap = per_group + G1_BLOCK, wgs = (size_t)sets * windows * groups;
-  return pad256((size_t)sets * n * G1_AFF_STRIDE * 4) + pad256((size_t)sets * windows * n * 2) + pad256(wgs * list_cap * 4) +
-         pad256(wgs * G1_BLOCK * G1_PT_WORDS * 4) + pad256(wgs * G1_PT_WORDS * 4) + 256 + 256;
-}
-G1MsmLayout g1_msm_layout(size_t n, int sets, int windows, int groups, void* ws) {
-  G1MsmLayout L;
+// the regions of `sets` MSMs over n points each (own_pts) or over n shared points held elsewhere; the callers add their tails
+static void g1_carve(MsmCarve& c, G1MsmLayout& L, size_t n, int sets, int windows, int groups, bool own_pts) {
   L.n = n; L.sets = sets; L.windows = windows; L.groups = groups;
   L.per_group = (n + groups - 1) / groups;
   L.list_cap = L.per_group + G1_BLOCK;
-  const size_t wgs = (size_t)sets * windows * groups;
-  uint8_t* p = static_cast<uint8_t*>(ws);
-  L.pts = reinterpret_cast<uint32_t*>(p); p += pad256((size_t)sets * n * G1_AFF_STRIDE * 4);
-  L.digits = reinterpret_cast<int16_t*>(p); p += pad256((size_t)sets * windows * n * 2);
-  L.lists = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * L.list_cap * 4);
-  L.heads = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * G1_BLOCK * G1_PT_WORDS * 4);
-  L.part = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * G1_PT_WORDS * 4);
-  L.sums = p; p += 256;
-  L.flags = p;
+  const MsmRegions r = msm_carve_regions<G1Msm>(c, own_pts ? (size_t)sets * n : 0, (size_t)sets * windows, n,
+                                                 (size_t)sets * windows * groups, L.list_cap);
+  L.pts = r.pts; L.digits = r.digits; L.lists = r.lists; L.heads = r.heads; L.part = r.part;
+}
+static G1MsmLayout g1_msm_carve(MsmCarve& c, size_t n, int sets, int windows, int groups) {
+  G1MsmLayout L;
+  g1_carve(c, L, n, sets, windows, groups, true);
+  L.sums = c.take<uint8_t>(256);
+  L.flags = c.take<uint8_t>(256);
   return L;
+}
+size_t g1_msm_workspace_bytes(size_t n, int sets, int windows, int groups) {
+  MsmCarve c(nullptr);
+  g1_msm_carve(c, n, sets, windows, groups);
+  return c.off;
+}
+G1MsmLayout g1_msm_layout(size_t n, int sets, int windows, int groups, void* ws) {
+  MsmCarve c(ws);
+  return g1_msm_carve(c, n, sets, windows, groups);
 }
 
 void launch_g1_buckets(const G1MsmLayout& L, hipStream_t st, bool shared_pts) {
-  const size_t lds_bytes = ((size_t)G1_BUCKETS * G1_PT_WORDS + 2 * G1_BUCKETS + 16) * 4;      // 90,176 B
+  const size_t lds_bytes = msm_bucket_lds_bytes<G1Msm>();      // 90,176 B
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_g1_buckets<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -364,27 +265,24 @@ void launch_g1_buckets(const G1MsmLayout& L, hipStream_t st, bool shared_pts) {
 void launch_g1_final(const G1MsmLayout& L, hipStream_t st) {
   hipLaunchKernelGGL(k_g1_final, dim3((unsigned)L.sets), dim3(G1_FINAL_BLOCK), 0, st, L);
 }
+static G1MsmLayout g1_shared_carve(MsmCarve& c, size_t n, int sets, int groups, size_t q_wgs, uint32_t** wg_sums) {
+  G1MsmLayout L;
+  g1_carve(c, L, n, sets, G1_W_FULL, groups, false);
+  *wg_sums = c.take<uint32_t>((size_t)sets * q_wgs * KZG_PART_WORDS * 4);
+  L.sums = c.take<uint8_t>((size_t)sets * 96);
+  L.flags = c.take<uint8_t>((size_t)sets);
+  return L;
+}
 size_t g1_shared_workspace_bytes(size_t n, int sets, int groups, size_t q_wgs) {
-  const size_t per_group = (n + groups - 1) / groups, list_cap = per_group + G1_BLOCK, wgs = (size_t)sets * G1_W_FULL * groups;
-  return pad256((size_t)sets * G1_W_FULL * n * 2) + pad256(wgs * list_cap * 4) + pad256(wgs * G1_BLOCK * G1_PT_WORDS * 4) +
-         pad256(wgs * G1_PT_WORDS * 4) + pad256((size_t)sets * q_wgs * KZG_PART_WORDS * 4) + pad256((size_t)sets * 96) +
-         pad256((size_t)sets);
+  MsmCarve c(nullptr);
+  uint32_t* wg_sums;
+  g1_shared_carve(c, n, sets, groups, q_wgs, &wg_sums);
+  return c.off;
 }
 G1MsmLayout g1_shared_layout(size_t n, int sets, int groups, size_t q_wgs, void* ws, uint32_t* pts, uint32_t** wg_sums) {
-  G1MsmLayout L;
-  L.n = n; L.sets = sets; L.windows = G1_W_FULL; L.groups = groups;
-  L.per_group = (n + groups - 1) / groups;
-  L.list_cap = L.per_group + G1_BLOCK;
-  const size_t wgs = (size_t)sets * G1_W_FULL * groups;
-  uint8_t* p = static_cast<uint8_t*>(ws);
+  MsmCarve c(ws);
+  G1MsmLayout L = g1_shared_carve(c, n, sets, groups, q_wgs, wg_sums);
   L.pts = pts;
-  L.digits = reinterpret_cast<int16_t*>(p); p += pad256((size_t)sets * G1_W_FULL * n * 2);
-  L.lists = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * L.list_cap * 4);
-  L.heads = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * G1_BLOCK * G1_PT_WORDS * 4);
-  L.part = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * G1_PT_WORDS * 4);
-  *wg_sums = reinterpret_cast<uint32_t*>(p); p += pad256((size_t)sets * q_wgs * KZG_PART_WORDS * 4);
-  L.sums = p; p += pad256((size_t)sets * 96);
-  L.flags = p;
   return L;
 }
 size_t g1_shared_secret_bytes(const G1MsmLayout& L) { return (size_t)(L.sums - reinterpret_cast<uint8_t*>(L.digits)); }

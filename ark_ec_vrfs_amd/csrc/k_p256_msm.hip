@@ -2,13 +2,12 @@
 // (`suites::secp256r1` x `VariableBaseMSM::msm` / `pedersen::Verifier`, /root/reference src/lib.rs:14; SURVEY.md section 8 rows
 // a14, f2, f4).  Compiled with -DVRF_FIELD=3 beside k_p256.hip; launch interface in p256.h.
 //
-// Pippenger with signed 10-bit windows and the window's 512 buckets in LDS (54 KiB), the schedule of k_msm.hip / k_msm_g1.hip:
+// Pippenger with signed 10-bit windows and the window's 512 buckets in LDS (54 KiB):
 //   k_pm_prep      : x || y (little-endian canonical or arkworks Montgomery limbs) -> Montgomery 9 x 29-bit limbs, on-curve
 //                    test; big-endian scalars < n -> folded (k or n - k) signed digits
-//   k_pm_buckets   : one workgroup per (window, point group): counting sort by bucket (LDS atomics, wave-shuffle scan), the
-//                    sorted list cut into 512 equal chunks, every lane folds its chunk with the COMPLETE addition of sw.cuh
-//                    (a bucket may meet P and -P, or P twice: no exceptional case to branch on), list entries fetched two
-//                    trips ahead and points one trip ahead of their use; heads merged; sum_j j B_j by suffix scan + tree
+//   k_pm_buckets   : one workgroup per (window, point group): the bucket pass of msm_buckets.cuh, every lane folding its chunk
+//                    with the COMPLETE addition of sw.cuh (a bucket may meet P and -P, or P twice: no exceptional case to
+//                    branch on)
 //   k_pm_final     : per window the sum of its groups, 10 w Jacobian doublings, tree-sum, then Sec1 / x || y -- or, for the
 //                    batched verifier, only "is it the point at infinity"
 // Batched Pedersen verification (k_pm_rlc_*): with 128-bit weights z_i, z'_i drawn from a digest of every input byte,
@@ -20,6 +19,7 @@
 #include <cstring>
 #include "p256.h"
 #include "p256_core.cuh"
+#include "msm_buckets.cuh"
 
 VRF_NS_BEGIN
 namespace {
@@ -29,53 +29,13 @@ constexpr int PM_C = p256::MSM_C, PM_BUCKETS = 1 << (PM_C - 1), PM_BLOCK = PM_BU
 constexpr int PM_PT = PTW_WORDS;                       // 27 words: projective bucket / partial sum
 constexpr int PM_AFF = p256::MSM_AFF_STRIDE;           // 32-word slot of an affine point (18 used): one cache line per gather
 constexpr int PM_IDX_BITS = 21;
-constexpr uint32_t PM_IDX_MASK = (1u << PM_IDX_BITS) - 1, PM_NONE = 0xffffffffu;
 static_assert(PM_W * PM_C >= 257 && 2 * NL <= PM_AFF, "window count / slot size");
 
 __device__ __forceinline__ void pm_store(uint32_t* dst, const PtW& p) { ptw_store(dst, 1, p); }
 __device__ __forceinline__ PtW pm_load(const uint32_t* src) { return ptw_load(src, 1); }
 
-// signed radix-2^10 digits of k (< n, little-endian words), folded to min(k, n - k) with the sign flipped; `negate` flips
-// the term, `zero` drops the point
-__device__ void pm_write_digits(int16_t* digits, size_t n, size_t i, const uint32_t k_in[8], bool negate, bool zero) {
-  uint32_t k[8], nk[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) k[j] = zero ? 0u : k_in[j];
-  {
-    uint32_t borrow = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint64_t d = (uint64_t)CurveP256::r32(j) - k[j] - borrow;
-      nk[j] = (uint32_t)d;
-      borrow = (uint32_t)(d >> 63);
-    }
-  }
-  bool flip = false, decided = false;
-#pragma unroll
-  for (int j = 7; j >= 0; --j)
-    if (!decided && nk[j] != k[j]) { flip = nk[j] < k[j]; decided = true; }
-  flip = flip && !zero;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) k[j] = flip ? nk[j] : k[j];
-  const bool neg = flip != negate;
-  uint32_t carry = 0;
-#pragma unroll 1
-  for (int w = 0; w < PM_W; ++w) {
-    const int bit = w * PM_C, wi = bit >> 5, sh = bit & 31;
-    uint32_t lo = 0, hi = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (j == wi) lo = k[j];
-      if (j == wi + 1) hi = k[j];
-    }
-    uint32_t v = (sh ? ((lo >> sh) | (hi << (32 - sh))) : lo) & ((1u << PM_C) - 1);
-    v += carry;
-    int d = (int)v;
-    carry = 0;
-    if (v > (uint32_t)PM_BUCKETS) { d = (int)v - (1 << PM_C); carry = 1; }
-    digits[(size_t)w * n + i] = (int16_t)(neg ? -d : d);
-  }
-}
+// digits: signed radix-2^10 of k (< n, little-endian words) folded to min(k, n - k) with the sign flipped
+// (msm_write_folded_digits<PM_C, PM_W, CurveP256>); `negate` flips the term, `zero` drops the point
 __device__ __forceinline__ void pm_store_affine(uint32_t* slot, const FeN& x, const FeN& y) {
 #pragma unroll
   for (int j = 0; j < NL; ++j) { slot[j] = x.v[j]; slot[NL + j] = y.v[j]; }
@@ -100,7 +60,7 @@ __global__ void __launch_bounds__(128) k_pm_prep(MsmL L, const uint8_t* xy, cons
   const bool ok = fr_is_canonical<CurveP256>(kw) && !u256_ge_q(xin) && !u256_ge_q(yin) && (inf || sw_on_curve(x, y));
   if (!ok) L.flags[0] = 2;
   pm_store_affine(L.pts + i * PM_AFF, x, y);
-  pm_write_digits(L.digits, L.n, i, k, false, !ok || inf);
+  msm_write_folded_digits<PM_C, PM_W, CurveP256>(L.digits, L.n, i, k, false, !ok || inf);
 }
 
 // P + (x2, y2) for any P (the point at infinity included) and an AFFINE second operand (RCB 2016 algorithm 5, a = -3):
@@ -131,13 +91,30 @@ VRF_HD PtW sw_madd(const PtW& p, const FeN& x2, const FeN& y2) {
 }
 
 // ------------------------------------------------------------------------------- buckets
+// the secp256r1 instantiation of msm_bucket_pass (msm_buckets.cuh): projective accumulators, affine (x, y) inputs added as +-y
+struct PmAff { FeN x, y; };
+struct PmMsm {
+  using Acc = PtW;
+  using Aff = PmAff;
+  static constexpr int BLOCK = PM_BLOCK, BPL = 1, PT_WORDS = PM_PT, AFF_STRIDE = PM_AFF, IDX_BITS = PM_IDX_BITS;
+  static constexpr int HIST_LOADS = 4, SCATTER_LOADS = 1;
+  static VRF_HD PtW identity() { return sw_identity(); }
+  static VRF_HD PtW load(const uint32_t* src) { return pm_load(src); }
+  static VRF_HD void store(uint32_t* dst, const PtW& p) { pm_store(dst, p); }
+  static VRF_HD PmAff aff_load(const uint32_t* src) {
+    PmAff a;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) { a.x.v[j] = src[j]; a.y.v[j] = src[NL + j]; }
+    return a;
+  }
+  static VRF_HD PmAff aff_identity() { return PmAff{fe_zero(), fe_one()}; }
+  static VRF_HD PtW madd(const PtW& p, const PmAff& q, bool neg) { return sw_madd(p, q.x, fe_select(neg, fe_wred(fe_neg(q.y)), q.y)); }
+  static VRF_HD PtW add(const PtW& p, const PtW& q) { return sw_add(p, q); }
+};
+static_assert(PM_BLOCK * PmMsm::BPL == PM_BUCKETS, "one bucket per lane");
+
 __global__ void __launch_bounds__(PM_BLOCK) k_pm_buckets(MsmL L) {
   extern __shared__ uint32_t lds[];
-  uint32_t* bucket = lds;                                   // [512][27]
-  uint32_t* counts = lds + PM_BUCKETS * PM_PT;              // [512]
-  uint32_t* cursor = counts + PM_BUCKETS;                   // [512] scatter cursors, later head bucket ids
-  uint32_t* wsum = cursor + PM_BUCKETS;                     // [8]
-  const int t = threadIdx.x;
   const int wg = blockIdx.x;
   // the grid holds the low windows' workgroups (MSM_W_SHORT x groups) and then the high windows' (x groups_hi): the windows a
   // bare 128-bit weight cannot reach hold the full-size scalars only, in fewer groups of about the same size
@@ -148,133 +125,14 @@ __global__ void __launch_bounds__(PM_BLOCK) k_pm_buckets(MsmL L) {
   const size_t span = high ? L.per_group_hi : L.per_group, end = high ? L.n_long : L.n;
   const size_t lo = (size_t)g * span;
   const size_t hi = lo + span < end ? lo + span : end;
-  const uint32_t cnt_all = lo < hi ? (uint32_t)(hi - lo) : 0u;
-  const int16_t* dig = L.digits + (size_t)w * L.n + lo;
-  const uint32_t* P = L.pts + lo * PM_AFF;
-  uint32_t* list = L.lists + (size_t)wg * L.list_cap;
-  uint32_t* heads = L.heads + (size_t)wg * PM_BLOCK * PM_PT;
-  pm_store(bucket + t * PM_PT, sw_identity());
-  // 1. histogram
-  counts[t] = 0;
-  __syncthreads();
-  for (uint32_t j0 = t; j0 < cnt_all; j0 += 4 * PM_BLOCK) {
-    int d[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const uint32_t j = j0 + u * PM_BLOCK;
-      d[u] = j < cnt_all ? dig[j] : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (d[u] != 0) atomicAdd(&counts[(d[u] < 0 ? -d[u] : d[u]) - 1], 1u);
-  }
-  __syncthreads();
-  // 2. exclusive scan of the 512 counts
-  uint32_t m;
-  {
-    const uint32_t v = counts[t];
-    uint32_t incl = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-      const uint32_t u = __shfl_up(incl, s, 64);
-      if ((t & 63) >= s) incl += u;
-    }
-    if ((t & 63) == 63) wsum[t >> 6] = incl;
-    __syncthreads();
-    uint32_t wbase = 0, total = 0;
-    for (int k = 0; k < PM_BLOCK / 64; ++k) {
-      const uint32_t x = wsum[k];
-      if (k < (t >> 6)) wbase += x;
-      total += x;
-    }
-    m = total;
-    cursor[t] = wbase + incl - v;
-  }
-  __syncthreads();
-  // 3. scatter into bucket order, transposed: entry i of lane l sits at list[i * 512 + l]
-  const uint32_t chunk = (m + PM_BLOCK - 1) / PM_BLOCK;
-  for (uint32_t j = t; j < cnt_all; j += PM_BLOCK) {
-    const int d = dig[j];
-    if (d != 0) {
-      const uint32_t b = (uint32_t)(d < 0 ? -d : d) - 1;
-      const uint32_t pos = atomicAdd(&cursor[b], 1u);
-      const uint32_t lane = pos / chunk, i = pos - lane * chunk;
-      list[(size_t)i * PM_BLOCK + lane] = j | (b << PM_IDX_BITS) | (d < 0 ? 0x80000000u : 0u);
-    }
-  }
-  __threadfence_block();
-  __syncthreads();
-  // 4. every lane folds its chunk (same trip count for all lanes); entries two trips ahead, points one trip ahead
-  uint32_t head_b = PM_NONE;
-  {
-    const uint32_t my0 = (uint32_t)t * chunk;
-    const uint32_t cnt = my0 >= m ? 0u : (m - my0 < chunk ? m - my0 : chunk);
-    PtW acc = sw_identity();
-    uint32_t cur = PM_NONE;
-    bool first_run = true;
-    uint32_t* myhead = heads + (size_t)t * PM_PT;
-    auto load_xy = [&](FeN& x, FeN& y, uint32_t e) {
-      const uint32_t* src = P + (size_t)(e & PM_IDX_MASK) * PM_AFF;
-#pragma unroll
-      for (int j = 0; j < NL; ++j) { x.v[j] = src[j]; y.v[j] = src[NL + j]; }
-    };
-    uint32_t ent_n = 0, ent_nn = 0;
-    FeN x_n = fe_zero(), y_n = fe_one();
-    if (cnt > 0) ent_n = list[t];
-    if (cnt > 1) ent_nn = list[(size_t)PM_BLOCK + t];
-    if (cnt > 0) load_xy(x_n, y_n, ent_n);
-#pragma unroll 1
-    for (uint32_t i = 0; i < chunk; ++i) {
-      if (i < cnt) {
-        const uint32_t ent = ent_n;
-        const FeN x = x_n, y = y_n;
-        ent_n = ent_nn;
-        if (i + 2 < cnt) ent_nn = list[(size_t)(i + 2) * PM_BLOCK + t];
-        if (i + 1 < cnt) load_xy(x_n, y_n, ent_n);
-        const uint32_t b = (ent >> PM_IDX_BITS) & (PM_BUCKETS - 1);
-        if (b != cur) {
-          if (cur != PM_NONE) {
-            if (first_run) { pm_store(myhead, acc); head_b = cur; first_run = false; }
-            else pm_store(bucket + cur * PM_PT, acc);
-          }
-          cur = b;
-          acc = sw_identity();
-        }
-        acc = sw_madd(acc, x, fe_select((ent >> 31) != 0, fe_wred(fe_neg(y)), y));
-      }
-    }
-    if (cnt > 0) {
-      if (first_run) { pm_store(myhead, acc); head_b = cur; }
-      else pm_store(bucket + cur * PM_PT, acc);
-    }
-  }
-  cursor[t] = head_b;
-  __threadfence_block();
-  __syncthreads();
-  // 5. merge the heads: the first lane of each chain of equal head buckets adds the chain to the bucket
-  if (head_b != PM_NONE && (t == 0 || cursor[t - 1] != head_b)) {
-    PtW h = pm_load(heads + (size_t)t * PM_PT);
-    for (int k = t + 1; k < PM_BLOCK && cursor[k] == head_b; ++k) h = sw_add(h, pm_load(heads + (size_t)k * PM_PT));
-    uint32_t* slot = bucket + head_b * PM_PT;
-    pm_store(slot, sw_add(pm_load(slot), h));
-  }
-  __syncthreads();
-  // 6. R = sum_j j B_j: lane t holds B_{t+1}; suffix scan S_t = sum_{u >= t} B_{u+1}, then R = sum_t S_t
-  PtW cur = pm_load(bucket + t * PM_PT);
-  uint32_t* stage = lds;
-#pragma unroll 1
-  for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll 1
-    for (int k = 0; k < 9; ++k) {
-      const int s = pass == 0 ? (1 << k) : (PM_BLOCK >> (k + 1));
-      __syncthreads();
-      pm_store(stage + t * PM_PT, cur);
-      __syncthreads();
-      const bool active = pass == 0 ? (t + s < PM_BLOCK) : (t < s);
-      if (active) cur = sw_add(cur, pm_load(stage + (t + s) * PM_PT));
-    }
-  }
-  if (t == 0) pm_store(L.part + ((size_t)w * L.groups + g) * PM_PT, cur);
+  MsmBucketJob job;
+  job.digits = L.digits + (size_t)w * L.n + lo;
+  job.pts = L.pts + lo * PM_AFF;
+  job.count = lo < hi ? (uint32_t)(hi - lo) : 0u;
+  job.list = L.lists + (size_t)wg * L.list_cap;
+  job.heads = L.heads + (size_t)wg * PM_BLOCK * PM_PT;
+  job.out = L.part + ((size_t)w * L.groups + g) * PM_PT;
+  msm_bucket_pass<PmMsm>(job, lds);
 }
 
 // ------------------------------------------------------------------------------- final
@@ -394,15 +252,15 @@ __global__ void __launch_bounds__(128) k_pm_rlc_decode(p256::RlcArgs a) {
   const size_t n = a.n;
   // x / y order of the decode: H, Gamma, pk_com, R, Ok
   pm_store_affine(L.pts + pm_rlc_index(0, n, i) * PM_AFF, x[0], y[0]);       // + z s   H
-  pm_write_digits(L.digits, L.n, pm_rlc_index(0, n, i), zs, false, !ok);
+  msm_write_folded_digits<PM_C, PM_W, CurveP256>(L.digits, L.n, pm_rlc_index(0, n, i), zs, false, !ok);
   pm_store_affine(L.pts + pm_rlc_index(1, n, i) * PM_AFF, x[1], y[1]);       // - z c   Gamma
-  pm_write_digits(L.digits, L.n, pm_rlc_index(1, n, i), zc, true, !ok);
+  msm_write_folded_digits<PM_C, PM_W, CurveP256>(L.digits, L.n, pm_rlc_index(1, n, i), zc, true, !ok);
   pm_store_affine(L.pts + pm_rlc_index(2, n, i) * PM_AFF, x[2], y[2]);       // - z' c  pk_com
-  pm_write_digits(L.digits, L.n, pm_rlc_index(2, n, i), zpc, true, !ok);
+  msm_write_folded_digits<PM_C, PM_W, CurveP256>(L.digits, L.n, pm_rlc_index(2, n, i), zpc, true, !ok);
   pm_store_affine(L.pts + pm_rlc_index(3, n, i) * PM_AFF, x[4], y[4]);       // - z     Ok
-  pm_write_digits(L.digits, L.n, pm_rlc_index(3, n, i), z, true, !ok);
+  msm_write_folded_digits<PM_C, PM_W, CurveP256>(L.digits, L.n, pm_rlc_index(3, n, i), z, true, !ok);
   pm_store_affine(L.pts + pm_rlc_index(4, n, i) * PM_AFF, x[3], y[3]);       // - z'    R
-  pm_write_digits(L.digits, L.n, pm_rlc_index(4, n, i), zp, true, !ok);
+  msm_write_folded_digits<PM_C, PM_W, CurveP256>(L.digits, L.n, pm_rlc_index(4, n, i), zp, true, !ok);
   // sum z' s and sum z' sb: 32-bit limbs into 64-bit columns (2^20 terms of 2^32 stay far below 2^64)
   if (ok) {
 #pragma unroll
@@ -439,14 +297,12 @@ __global__ void k_pm_rlc_fixed(p256::RlcArgs a) {
   }
   const size_t idx = 3 * a.n + f;
   pm_store_affine(a.L.pts + idx * PM_AFF, fe_from_u256(xin), fe_from_u256(yin));
-  pm_write_digits(a.L.digits, a.L.n, idx, k, false, false);
+  msm_write_folded_digits<PM_C, PM_W, CurveP256>(a.L.digits, a.L.n, idx, k, false, false);
 }
-
-size_t pad256(size_t x) { return (x + 255) & ~size_t(255); }
 
 void launch_core(const MsmL& L, uint8_t* out33, uint8_t* out_xy, int xy_mont256, uint8_t* status1, uint8_t* fail_flag, hipStream_t st,
                  hipEvent_t* ev) {
-  const size_t lds_bytes = ((size_t)PM_BUCKETS * PM_PT + 2 * PM_BUCKETS + 16) * 4;
+  const size_t lds_bytes = msm_bucket_lds_bytes<PmMsm>();
   const unsigned wgs = (unsigned)(p256::MSM_W_SHORT * L.groups + (PM_W - p256::MSM_W_SHORT) * L.groups_hi);
   hipLaunchKernelGGL(k_pm_buckets, dim3(wgs), dim3(PM_BLOCK), lds_bytes, st, L);
   if (ev) (void)hipEventRecord(ev[2], st);
@@ -489,32 +345,33 @@ int msm_groups(size_t n, size_t n_long, int cus) {
   if ((size_t)g < min_g) g = (int)min_g;
   return g;
 }
+// the regions of an MSM over n points in `groups` groups, sized for the worst case groups_hi == groups
+static void msm_carve(MsmCarve& c, MsmL& L, size_t n, int groups) {
+  L.per_group = (n + groups - 1) / groups;
+  L.list_cap = L.per_group + PM_BLOCK;
+  const MsmRegions r = msm_carve_regions<PmMsm>(c, n, MSM_W, n, (size_t)MSM_W * groups, L.list_cap);
+  L.pts = r.pts; L.digits = r.digits; L.lists = r.lists; L.heads = r.heads; L.part = r.part;
+  L.flags = c.take<uint8_t>(256);
+  L.cols = c.take<unsigned long long>(256);
+}
 size_t msm_workspace_bytes(size_t n, int groups) {
-  const size_t per_group = (n + groups - 1) / groups, list_cap = per_group + PM_BLOCK, wgs = (size_t)MSM_W * groups;
-  return pad256(n * PM_AFF * 4) + pad256((size_t)MSM_W * n * 2) + pad256(wgs * list_cap * 4) + pad256(wgs * PM_BLOCK * PM_PT * 4) +
-         pad256(wgs * PM_PT * 4) + 256 + 256;
+  MsmL L;
+  MsmCarve c(nullptr);
+  msm_carve(c, L, n, groups);
+  return c.off;
 }
 MsmL msm_layout(size_t n, size_t n_long, int groups, void* ws) {
   MsmL L;
+  MsmCarve c(ws);
+  msm_carve(c, L, n, groups);
   L.n = n; L.groups = groups;
   L.n_long = n_long < n ? n_long : n;
-  L.per_group = (n + groups - 1) / groups;
   int gh = (int)(((double)L.n_long / (double)(n ? n : 1)) * groups + 0.999);
   if (gh < 1) gh = 1;
   if (gh > groups) gh = groups;
   L.groups_hi = gh;
   L.per_group_hi = (L.n_long + gh - 1) / gh;
   if (L.per_group_hi > L.per_group) { L.groups_hi = groups; L.per_group_hi = (L.n_long + groups - 1) / groups; }
-  L.list_cap = L.per_group + PM_BLOCK;
-  const size_t wgs = (size_t)MSM_W * groups;
-  uint8_t* p = static_cast<uint8_t*>(ws);
-  L.pts = reinterpret_cast<uint32_t*>(p); p += pad256(n * PM_AFF * 4);
-  L.digits = reinterpret_cast<int16_t*>(p); p += pad256((size_t)MSM_W * n * 2);
-  L.lists = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * L.list_cap * 4);
-  L.heads = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * PM_BLOCK * PM_PT * 4);
-  L.part = reinterpret_cast<uint32_t*>(p); p += pad256(wgs * PM_PT * 4);
-  L.flags = p; p += 256;
-  L.cols = reinterpret_cast<unsigned long long*>(p);
   return L;
 }
 

@@ -7,6 +7,7 @@
 // top window never carries out.
 #pragma once
 #include "vrf_core.cuh"
+#include "msm_buckets.cuh"
 
 VRF_NS_BEGIN
 
@@ -43,46 +44,8 @@ constexpr int MSM_W_SHORT = 12;                   // windows a scalar < 2^128 ca
 // canonical scalar k (< r) -> folded signed radix-2^11 digits of point i.  `negate` flips the sign of the
 // term (callers that subtract a term); `zero` drops the point from the sum.
 template <class S>
-VRF_HD void msm_write_digits(int16_t* digits, size_t n, size_t i, const uint32_t k_in[8], bool negate,
-                             bool zero) {
-  uint32_t k[8], nk[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) k[j] = zero ? 0u : k_in[j];
-  {
-    uint32_t borrow = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      uint64_t d = (uint64_t)S::r32(j) - k[j] - borrow;
-      nk[j] = (uint32_t)d;
-      borrow = (uint32_t)(d >> 63);
-    }
-  }
-  // fold: k > r - k  ->  use r - k and flip the sign of every digit
-  bool flip = false, decided = false;
-#pragma unroll
-  for (int j = 7; j >= 0; --j)
-    if (!decided && nk[j] != k[j]) { flip = nk[j] < k[j]; decided = true; }
-  flip = flip && !zero;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) k[j] = flip ? nk[j] : k[j];
-  const bool neg = flip != negate;
-  uint32_t carry = 0;
-#pragma unroll 1
-  for (int w = 0; w < MSM_W; ++w) {
-    int bit = w * MSM_C, wi = bit >> 5, sh = bit & 31;
-    uint32_t lo = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) if (j == wi) lo = k[j];
-    uint32_t hi = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) if (j == wi + 1) hi = k[j];
-    uint32_t v = (sh ? ((lo >> sh) | (hi << (32 - sh))) : lo) & ((1u << MSM_C) - 1);
-    v += carry;
-    int d = (int)v;
-    carry = 0;
-    if (v > (uint32_t)MSM_BUCKETS) { d = (int)v - (1 << MSM_C); carry = 1; }
-    digits[(size_t)w * n + i] = (int16_t)(neg ? -d : d);
-  }
+VRF_HD void msm_write_digits(int16_t* digits, size_t n, size_t i, const uint32_t k[8], bool negate, bool zero) {
+  msm_write_folded_digits<MSM_C, MSM_W, S>(digits, n, i, k, negate, zero);
 }
 
 // MSM index of point class p (H, Gamma, pk_com, R, Ok) of proof i: the classes with full-size scalars

@@ -1,6 +1,8 @@
 // tests/hostsim -- TEST TOOLING ONLY: host build of the BLS12-381 pairing headers.
 #include "../../ark_ec_vrfs_amd/csrc/bls12.cuh"
 #include "../../ark_ec_vrfs_amd/csrc/g1.cuh"
+#include "../../ark_ec_vrfs_amd/csrc/msm_g1.h"
+#include "../../ark_ec_vrfs_amd/csrc/msm_buckets.cuh"
 #include <cstring>
 #include <vector>
 using namespace bls;
@@ -127,5 +129,10 @@ void hb_g1_chain(uint32_t n, const uint8_t* pts, const uint8_t* signs, uint32_t 
   for (uint32_t i = 0; i < n; ++i) acc = g1_madd(acc, inw(pts + 96 * i), inw(pts + 96 * i + 48), signs[i] != 0);
   for (uint32_t i = 0; i < dbl; ++i) acc = g1_dbl(acc);
   g1_out(r, acc);
+}
+// ---- MSM digit recoding (msm_buckets.cuh) as g1_write_digits calls it: k little-endian, W = G1_W_SHORT or G1_W_FULL windows ----
+void hb_msm_digits(const uint8_t* k, int W, int negate, int zero, int16_t* out) {
+  uint32_t w[8]; memcpy(w, k, 32);
+  vrf::msm_recode_windows<vrf::G1_C>(out, 1, 0, W, w, negate != 0, zero != 0);
 }
 }

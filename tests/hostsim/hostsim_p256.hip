@@ -2,6 +2,8 @@
 // complete short-Weierstrass law, SHA-256 / HMAC, the Sec1 codec, try-and-increment, the RFC 6979 nonce and the per-item
 // prove / verify steps exactly as k_p256.hip composes them.  Never linked into libvrfhip.so.
 #include "../../ark_ec_vrfs_amd/csrc/p256_core.cuh"
+#include "../../ark_ec_vrfs_amd/csrc/p256.h"
+#include "../../ark_ec_vrfs_amd/csrc/msm_buckets.cuh"
 #include <cstring>
 #include <vector>
 using namespace vrf;
@@ -249,5 +251,12 @@ int hp_prove_cases(int pedersen, int ct, const uint8_t* sk_be, const uint8_t* h_
   store_be256(o + 65, s);
   sec1_store(o + 130, henc.tag, henc.xw);
   return 0;
+}
+// ---- MSM digit recoding (msm_buckets.cuh) with k_p256_msm.hip's parameters: k little-endian, < n ----
+void hp_msm_digits(const uint8_t* k, int negate, int zero, int16_t* out26) {
+  uint32_t w[8]; memcpy(w, k, 32);
+  int16_t d[p256::MSM_W];
+  msm_write_folded_digits<p256::MSM_C, p256::MSM_W, CurveP256>(d, 1, 0, w, negate != 0, zero != 0);
+  memcpy(out26, d, sizeof d);
 }
 }

@@ -266,30 +266,54 @@ def test_multi_proof_prepare_matches_oracle(hs):
         assert row == b"".join(r[k][i].tobytes() for k in ("output", "c", "s", "pk", "input")), i
 
 
+def _hostsim_lib(name):
+    so = os.path.join(HERE, name)
+    subprocess.run(["make", "-C", HERE, "-j4", name], check=True, stdout=subprocess.DEVNULL)
+    return ctypes.CDLL(so)
+
+
 def test_msm_digit_recoding_and_rlc_weights(hs):
-    """msm.cuh: signed radix-2^11 digits (folded at r/2) rebuild +-k mod r, stay in [-1024, 1024], leave the
-    windows >= 12 empty for 128-bit scalars; the batched-verification weights are the two 16-byte halves of
+    """msm_buckets.cuh as every MSM calls it.  Folded at r/2 (msm.cuh: Bandersnatch and JubJub, 23 windows of 11 bits;
+    k_p256_msm.hip: secp256r1, 26 windows of 10 bits) and unfolded (g1_digits.cuh: BLS12-381 G1, 26 and 13 windows of 10 bits,
+    k < 2^(10 W - 1)): the signed radix-2^C digits rebuild +-k mod r (the unfolded ones +-k itself), stay in
+    [-2^(C-1), 2^(C-1)] (unfolded and not negated: above -2^(C-1)), leave the windows a 128-bit scalar cannot reach empty,
+    and are all zero for `zero`.  The batched-verification weights are the two 16-byte halves of
     SHA-512("vrfhip-rlc-v2" || seed || batch digest || u64_le(i)) with the low three bits forced to 001; the MSM index map puts G and B after the three classes
     with full-size scalars."""
     import hashlib
-    rnd = random.Random(11)
+    from oracle import bls_oracle, sw_oracle
+    hp, hb = _hostsim_lib("libhostsim_p256.so"), _hostsim_lib("libhostsim_bls.so")
     jj_r = o.jubjub_params().r
-    for suite, r in ((1, S.r), (2, jj_r)):
-        cases = [0, 1, 2, 1024, 1025, 2047, 2048, r - 1, r - 2, (r - 1) // 2, (r + 1) // 2, (1 << 128) - 1, 1 << 127,
-                 (1 << 132) - 1] + [rnd.randrange(r) for _ in range(300)] + [rnd.randrange(1 << 128) for _ in range(100)]
+    # name, digits(k, negate, zero, out), window bits, windows, windows of a 128-bit scalar, group order, folded, largest k
+    rows = [
+        ("bandersnatch", lambda k, ng, z, d: hs.hs_msm_digits(1, _b(k), ng, z, d), 11, 23, 12, S.r, True, S.r),
+        ("jubjub", lambda k, ng, z, d: hs.hs_msm_digits(2, _b(k), ng, z, d), 11, 23, 12, jj_r, True, jj_r),
+        ("secp256r1", lambda k, ng, z, d: hp.hp_msm_digits(_b(k), ng, z, d), 10, 26, 13, sw_oracle.N, True, sw_oracle.N),
+        ("g1 full", lambda k, ng, z, d: hb.hb_msm_digits(_b(k), 26, ng, z, d), 10, 26, 13, bls_oracle.R, False, bls_oracle.R),
+        ("g1 short", lambda k, ng, z, d: hb.hb_msm_digits(_b(k), 13, ng, z, d), 10, 13, 13, bls_oracle.R, False, 1 << 128),
+    ]
+    for name, digits, C, W, w_short, r, folded, k_end in rows:
+        rnd = random.Random(11)
+        half = 1 << (C - 1)
+        cases = [0, 1, 2, half, half + 1, 2 * half - 1, 2 * half, r - 1, r - 2, (r - 1) // 2, (r + 1) // 2, (1 << 128) - 1, 1 << 127,
+                 (1 << (C * w_short)) - 1] + [rnd.randrange(r) for _ in range(300)] + [rnd.randrange(1 << 128) for _ in range(100)]
+        cases = [k for k in cases if k < k_end]
+        assert len(cases) >= 100 + 8
         for k in cases:
             for negate in (0, 1):
-                d = (ctypes.c_int16 * 23)()
-                hs.hs_msm_digits(suite, _b(k), negate, 0, d)
+                d = (ctypes.c_int16 * W)()
+                digits(k, negate, 0, d)
                 digs = list(d)
-                assert all(-1024 <= x <= 1024 for x in digs)
-                val = sum(x << (11 * w) for w, x in enumerate(digs))
-                assert val % r == (-k if negate else k) % r
+                assert all(-half <= x <= half for x in digs), (name, k)
+                val = sum(x << (C * w) for w, x in enumerate(digs))
+                assert val % r == (-k if negate else k) % r, (name, k)
+                if not folded:
+                    assert val == (-k if negate else k) and (negate or all(x > -half for x in digs)), (name, k)
                 if k < (1 << 128):
-                    assert all(x == 0 for x in digs[12:])
-        d = (ctypes.c_int16 * 23)()
-        hs.hs_msm_digits(suite, _b(r - 5), 0, 1, d)
-        assert not any(d)
+                    assert all(x == 0 for x in digs[w_short:]), (name, k)
+        d = (ctypes.c_int16 * W)()
+        digits(k_end - 5, 0, 1, d)
+        assert not any(d), name
     seed, root = bytes(range(100, 132)), bytes(range(7, 39))
     for idx in (0, 1, 255, 1 << 20, (1 << 63) + 12345):
         z, zp = ctypes.create_string_buffer(32), ctypes.create_string_buffer(32)
